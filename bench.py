@@ -1,8 +1,12 @@
 """Headline benchmark: Msamples/s of the HIP path tracer on the synthetic 10M-triangle soup
 (BASELINE.json configs[2] / SURVEY.md §8d C3), 1920x1080, max_depth 5, tile-split across ranks.
 The render form is the library's choice (the persistent path kernel on this scene);
-config.form names it, and an untimed same-run leg reports north_star's wavefront layout beside it
-(wavefront_ms_per_step).
+config.form names it.
+
+A plain run sets up, warms up, times the K steps, writes the timed render's film (--dump-outputs DIR)
+and prints the line.  Everything else the line can hold takes runs of its own and is behind --full:
+the counting passes and the roofline, the per-kernel breakdown, the wavefront leg (the launch-per-stage
+layout beside the library's form, wavefront_ms_per_spp), the CPU baseline and the C2 / C4 side legs.
 
 A step is spp_per_step = ceil(--frame-spp / K) samples per pixel over the whole frame, so the K timed
 steps render the metric's 1024-spp frame (--frame-spp, default 1024; the driver's --steps 20 renders
@@ -12,10 +16,10 @@ tiles: a pixel's samples are one sequential chain through its sampler stream (cp
 The frame-end gather to rank 0 (RCCL via torch.distributed) is inside the timed region.
 value = W*H*K*spp_per_step / max-over-ranks time.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  Under torch.distributed.run (WORLD_SIZE set)
-each process is one rank and --gpus must equal the world size.  Without it, --gpus N > 1 starts the N
-ranks itself (a torch.distributed.run child, before anything touches the GPU) and fails loudly when
-fewer than N devices are visible.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  Under
+torch.distributed.run (WORLD_SIZE set) each process is one rank and --gpus must equal the world size.
+Without it, --gpus N > 1 starts the N ranks itself (a torch.distributed.run child, before anything
+touches the GPU) and fails loudly when fewer than N devices are visible.
 """
 from __future__ import annotations
 
@@ -328,6 +332,83 @@ def build_once_per_node(rank: int, build, export, adopt, barrier, tag: str, shm_
     return info
 
 
+BVH_CACHE_MIN_TRIS = 1_000_000   # smaller scenes build in less time than a cache is worth
+
+
+def build_params(args, capi, world: int) -> tuple:
+    """(build_kw for upload_scene / build_bvh_host, host build threads): the job's usable CPUs shared by
+    the ranks of this node (16 at most)."""
+    build_threads = max(2, min(16, host_cpus()["usable"] // max(1, world)))
+    return dict(max_leaf_size=args.leaf, intersect_cost=args.sah_isect, n_bins=args.bins, n_threads=build_threads,
+                builder={"sah": capi.BUILDER_SAH, "lbvh": capi.BUILDER_LBVH, "sbvh": capi.BUILDER_SBVH}[args.builder],
+                spatial_budget=args.spatial_budget), build_threads
+
+
+def bvh_cache_base(args, build_kw, capi):
+    """Where the host-built BVH2 of this run's scene is kept between runs, or None when the run has none
+    (a small scene, the GPU builder): <user cache dir>/akari_amd/bench_bvh_<key>, the key a hash of the
+    scene's arguments, the build parameters and the two native libraries, so that a rebuilt library or
+    another scene never meets an old tree.  The files are <base>_nodes.npy, <base>_tris.npy and, written
+    last, <base>.json (the build's figures)."""
+    if args.scene != "soup" or args.tris < BVH_CACHE_MIN_TRIS or args.builder == "lbvh":
+        return None
+    import hashlib
+    h = hashlib.blake2b(digest_size=12)
+    h.update(json.dumps({"scene": args.scene, "tris": args.tris, "build": build_kw}, sort_keys=True).encode())
+    for lib in (capi.LIB_PATH, capi.GEN_PATH):
+        h.update(lib.read_bytes())
+    cache_dir = Path(os.environ.get("XDG_CACHE_HOME") or Path.home() / ".cache") / "akari_amd"
+    return cache_dir / f"bench_bvh_{h.hexdigest()}"
+
+
+def load_cached_bvh(base):
+    """(nodes, tris, figures) of a complete cache entry, mapped read-only, or None."""
+    from akari_amd import capi
+    try:
+        meta = json.loads(Path(f"{base}.json").read_text())
+        nodes = np.load(f"{base}_nodes.npy", mmap_mode="r")
+        tris = np.load(f"{base}_tris.npy", mmap_mode="r")
+        sizes = (meta["n_nodes"],), (meta["n_tris"],)
+        float(meta["build_ms"]), float(meta["sah_cost"])
+    except (OSError, ValueError, KeyError, TypeError):   # missing, cut short or not this format: no entry
+        return None
+    if nodes.dtype != capi.NODE_DTYPE or tris.dtype != capi.TRI_DTYPE or (nodes.shape, tris.shape) != sizes:
+        return None
+    return nodes, tris, meta
+
+
+def prepare_cache(args):
+    """--prepare-cache (run by build()): build the BVH2 of this command's scene on the host, with the
+    product builder and the parameters a one-GPU run uses, and keep it where that run looks for it.  The
+    run adopts it through akr_hip_import_accel (validated against the scene, bit-identical results)
+    instead of spending its first 24 s on the same build.  Nothing to do when the entry exists."""
+    from akari_amd import capi, scene
+    build_kw, _ = build_params(args, capi, 1)
+    base = bvh_cache_base(args, build_kw, capi)
+    if base is None or load_cached_bvh(base) is not None:
+        return
+    if visible_gpu_count() == 0:
+        log("[prepare-cache] no GPU visible: no benchmark run here to prepare for")
+        return
+    cs = scene.compile_scene(scene.soup_scene(n_tris=args.tris))
+    nodes, tris, info = capi.build_bvh_host(cs.vertices, cs.indices, **build_kw)
+    try:
+        base.parent.mkdir(parents=True, exist_ok=True)
+        for name, a in (("nodes", nodes), ("tris", tris)):
+            tmp = Path(f"{base}_{name}.tmp.npy")
+            np.save(tmp, a)
+            os.replace(tmp, f"{base}_{name}.npy")
+        Path(f"{base}.json").write_text(json.dumps({"n_nodes": int(info.n_nodes), "n_tris": int(info.n_tris),
+                                                    "build_ms": float(info.build_ms), "sah_cost": float(info.sah_cost),
+                                                    "max_depth": int(info.max_depth)}))
+    except OSError as e:   # no room or no cache directory: the runs build the tree themselves
+        log(f"[prepare-cache] {base} not written ({e})")
+        for f in base.parent.glob(base.name + "*"):
+            f.unlink(missing_ok=True)
+        return
+    log(f"[prepare-cache] {base}: {info.n_nodes} nodes, built in {info.build_ms / 1e3:.1f}s")
+
+
 def launch_check(world: int, rank: int):
     """--launch-check: the rank plumbing without a GPU (gloo): every rank joins the group and
     all-gathers a packed film the size of its tile share; rank 0 prints the live world size."""
@@ -387,6 +468,25 @@ def side_leg(name, device, max_depth, tile, build_kw, stream_of):
                 "timed": False, "note": f"one render_device of {spp} spp after a 1-spp warmup, untimed leg of this run"}
 
 
+def dump_outputs(out_dir, parts, limit_bytes=60_000_000, seed=0):
+    """--dump-outputs: the film the timed render left, as a caller of render_device receives it (packed
+    tile order; with N ranks the gathered films one after the other): radiance.npy [pixels, 3] and
+    weight.npy [pixels], f32.  A film above `limit_bytes` is cut to a seeded sample of its pixels, the
+    same from run to run, whose slots pixel_index.npy holds (f64)."""
+    rad = np.concatenate([r for r, _ in parts]).astype(np.float32, copy=False)
+    wgt = np.concatenate([w for _, w in parts]).astype(np.float32, copy=False)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n = wgt.shape[0]
+    keep = limit_bytes // (4 * 4 + 8)    # rgb + weight in f32 and the index in f64 per pixel
+    if n > keep:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        rad, wgt = rad[idx], wgt[idx]
+        np.save(out / "pixel_index.npy", idx.astype(np.float64))
+    np.save(out / "radiance.npy", np.ascontiguousarray(rad))
+    np.save(out / "weight.npy", np.ascontiguousarray(wgt))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=0,
@@ -397,6 +497,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20,
                     help="timed steps K; a step renders ceil(--frame-spp / K) spp of the whole frame")
     ap.add_argument("--warmup", type=int, default=2, help="untimed steps before the timed region (one render)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, each in untimed runs of its own: the "
+                         "counting passes and the roofline, the per-kernel breakdown, the wavefront leg, the CPU "
+                         "baseline and the C2 / C4 side legs (--count-lines, --wavefront-spp, --cpu-baseline and "
+                         "--side-legs choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed render's film as DIR/radiance.npy and "
+                         "DIR/weight.npy (f32, packed tile order as render_device returns it; a fixed seeded "
+                         "sample of the pixels, named by DIR/pixel_index.npy, when the film exceeds 60 MB)")
+    ap.add_argument("--prepare-cache", action="store_true",
+                    help="build this command's BVH on the host and keep it in the user's cache directory for the "
+                         "one-GPU runs that follow (build() does this for the default scene); no GPU work")
     ap.add_argument("--frame-spp", type=int, default=1024,
                     help="spp the K timed steps render together at least (the metric's 1024-spp frame)")
     ap.add_argument("--scene", choices=["soup", "cornell", "hall"], default="soup",
@@ -454,6 +566,9 @@ def main():
                          "(prints the per-rank time; not a bench line for the driver)")
     args = ap.parse_args()
 
+    if args.prepare_cache:
+        prepare_cache(args)
+        return
     how, world = launch_plan(args.gpus, os.environ)
     if how == "spawn":
         sys.exit(spawn_ranks(world, sys.argv[1:], need_devices=not (args.launch_check or args.rehearse_one_gpu)))
@@ -463,6 +578,7 @@ def main():
         launch_check(world, rank)
         return
 
+    full = args.full
     import torch
     import torch.distributed as dist
     rehearse = args.rehearse_one_gpu and world > 1
@@ -503,11 +619,8 @@ def main():
     t_gen = time.time() - t0
     ctx = capi.HipContext(local)
     t_setup = time.perf_counter()
-    # host BVH build threads: the job's usable CPUs shared by the ranks of this node (16 at most)
-    build_threads = max(2, min(16, host_cpus()["usable"] // max(1, world)))
-    build_kw = dict(max_leaf_size=args.leaf, intersect_cost=args.sah_isect, n_bins=args.bins, n_threads=build_threads,
-                    builder={"sah": capi.BUILDER_SAH, "lbvh": capi.BUILDER_LBVH, "sbvh": capi.BUILDER_SBVH}[args.builder],
-                    spatial_budget=args.spatial_budget)
+    build_kw, build_threads = build_params(args, capi, world)
+    cached = None
     if world > 1:
         # the node's ranks build the scene's BVH once (8 concurrent 10M-triangle SBVH builds would share
         # the host's CPUs): rank 0 builds it, the others adopt its BVH2 (akr_hip_import_accel:
@@ -518,7 +631,18 @@ def main():
             adopt=lambda nodes, tris: scene.upload_scene(ctx, cs, bvh=(nodes, tris), n_threads=build_threads),
             barrier=dist.barrier, tag=os.environ.get("MASTER_PORT", "0"))
     else:
-        info = scene.upload_scene(ctx, cs, **build_kw)
+        # one rank adopts the tree build() left in the user's cache (prepare_cache: the same builder, the
+        # same parameters), when there is one
+        base = bvh_cache_base(args, build_kw, capi)
+        cached = load_cached_bvh(base) if base else None
+        if base and not cached:   # the run builds the tree itself (~24 s on C3): say why
+            others = sorted(p.name for p in base.parent.glob("bench_bvh_*.json"))
+            log(f"[rank {rank}] no cached BVH at {base}" + (f" (entries under other keys: {others}: another "
+                f"library build, scene or CPU count)" if others else " (bench.py --prepare-cache makes one)"))
+        if cached:
+            info = scene.upload_scene(ctx, cs, bvh=cached[:2], n_threads=build_threads)
+        else:
+            info = scene.upload_scene(ctx, cs, **build_kw)
     t_setup = time.perf_counter() - t_setup  # BVH2 build (or import) + wide collapse + upload
     if args.rays_per_lane != 1:
         ctx.set_option("rays_per_lane", args.rays_per_lane)
@@ -531,8 +655,10 @@ def main():
     for kv in args.opt:
         k, _, v = kv.partition("=")
         ctx.set_option(k, int(v))
+    # the build's own figures, whenever it ran (an adopted tree has none)
+    build_ms, sah_cost = (cached[2]["build_ms"], cached[2]["sah_cost"]) if cached else (info.build_ms, info.sah_cost)
     log(f"[rank {rank}] {args.scene} {cs.n_tris} tris gen {t_gen:.1f}s, BVH {info.n_nodes} nodes depth {info.max_depth} "
-        f"build {info.build_ms / 1e3:.1f}s sah {info.sah_cost:.1f}")
+        f"build {build_ms / 1e3:.1f}s{' (cached)' if cached else ''} sah {sah_cost:.1f}, setup {t_setup:.1f}s")
 
     split = args.emulate_world if (args.emulate_world > 1 and world == 1) else world
     tiles = tiles_for_rank(W, H, args.tile, rank, split)
@@ -555,27 +681,28 @@ def main():
         dist.all_gather_into_tensor(gathered, film.to(cdev))
     torch.cuda.synchronize(dev)
 
-    # untimed counting pass: traversal tests of one sample pass (algorithmic bytes)
-    ctx.set_option("count_tests", 1)
-    ctx.reset_stats()
-    ctx.set_option("stats", 1)
-    ctx.render_device(1, args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
-    torch.cuda.synchronize(dev)
-    counts = ctx.trace_counts()
-    cstats = ctx.kernel_stats()
-    pprof = ctx.path_profile()   # the counting build's phase clocks (persistent forms only)
-    lines = None
-    if pprof.get("waves") and args.count_lines and world == 1:
-        # distinct 128-B lines one sample pass reads, in a pass of its own: k_path's
-        # counting build marks every node / leaf / shading-record line in a bitmap (atomics: the clocks
-        # of the pass above stay clean)
-        ctx.set_option("count_lines", 1)
+    counts = cstats = pprof = lines = None
+    if full:
+        # untimed counting pass: traversal tests of one sample pass (algorithmic bytes)
+        ctx.set_option("count_tests", 1)
+        ctx.reset_stats()
+        ctx.set_option("stats", 1)
         ctx.render_device(1, args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
         torch.cuda.synchronize(dev)
-        lp = ctx.path_profile()
-        ctx.set_option("count_lines", 0)
-        lines = {k: lp[f"lines_{k}"] for k in ("nodes", "leaves", "shading")}
-    ctx.set_option("count_tests", 0)
+        counts = ctx.trace_counts()
+        cstats = ctx.kernel_stats()
+        pprof = ctx.path_profile()   # the counting build's phase clocks (persistent forms only)
+        if pprof.get("waves") and args.count_lines and world == 1:
+            # distinct 128-B lines one sample pass reads (roofline.lines_per_pass), in a pass of its own: k_path's
+            # counting build marks every node / leaf / shading-record line in a bitmap (atomics: the clocks
+            # of the pass above stay clean)
+            ctx.set_option("count_lines", 1)
+            ctx.render_device(1, args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
+            torch.cuda.synchronize(dev)
+            lp = ctx.path_profile()
+            ctx.set_option("count_lines", 0)
+            lines = {k: lp[f"lines_{k}"] for k in ("nodes", "leaves", "shading")}
+        ctx.set_option("count_tests", 0)
     ctx.reset_stats()
     # events around every launch cost nothing on a whole frame but ~6 % of an 8-way rank's step;
     # trace_closest (the roofline kernel) is timed live either way
@@ -620,45 +747,52 @@ def main():
     passes = ctx.render_info()["passes"]
     # sanity: every pixel of this rank got every sample of the timed render
     assert int(wgt[:npix].min().item()) == spp and int(wgt[:npix].max().item()) == spp
-    # untimed per-kernel breakdown (events on every launch) over a few more samples
-    ctx.reset_stats()
-    ctx.set_option("stats", 1)
-    ctx.render_device(min(spp, 4), args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
-    torch.cuda.synchronize(dev)
-    bstats = ctx.kernel_stats()
-    # wavefront form: the shadow trace timed alone (on the main stream, not overlapping the
-    # closest-hit trace of the next bounce), for its own roofline
-    iso = None
-    if "trace_shadow" in bstats:
+    if args.dump_outputs and rank == 0:
+        # the film as the timed render left it, before any further render writes the buffers again
+        host = (gathered if world > 1 else film).cpu().numpy().reshape(world, 4, maxpix)
+        sizes = [sum((x1 - x0) * (y1 - y0) for x0, y0, x1, y1 in tiles_for_rank(W, H, args.tile, r, split))
+                 for r in range(world)] if world > 1 else [npix]
+        dump_outputs(args.dump_outputs, [(host[r, :3].reshape(-1)[:3 * n].reshape(n, 3), host[r, 3, :n])
+                                         for r, n in enumerate(sizes)])
+    bstats = iso = wavefront = None
+    if full:
+        # untimed per-kernel breakdown (events on every launch) over a few more samples
         ctx.reset_stats()
-        ctx.set_option("serial_shadow", 1)
+        ctx.set_option("stats", 1)
         ctx.render_device(min(spp, 4), args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
         torch.cuda.synchronize(dev)
-        iso = ctx.kernel_stats()
-        ctx.set_option("serial_shadow", 0)
-    # untimed same-run leg in north_star's layout (wavefront: raygen -> closest -> shade -> shadow
-    # -> splat launches per bounce), when the timed render ran a persistent kernel
-    wavefront = None
-    if rank == 0 and args.wavefront_spp > 0 and form["form"] in ("k_path", "k_path_defer", "k_path_spec"):
-        # the wavefront, whatever form the timed render ran; the options in effect before are
-        # restored afterwards
-        saved = {k: ctx.option_set(k) for k in ("stats", "path")}
-        ctx.reset_stats()
-        ctx.set_option("stats", 0)
-        ctx.set_option("path", 0)
-        ctx.render_device(1, args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)   # warm
-        torch.cuda.synchronize(dev)
-        tw = time.perf_counter()
-        ctx.render_device(args.wavefront_spp, args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
-        torch.cuda.synchronize(dev)
-        tw = time.perf_counter() - tw
-        wform = ctx.render_form()["form"]
-        for k, v in saved.items():
-            if v is not None:   # every one of them was set above (bench options / --opt)
-                ctx.set_option(k, v)
-        wavefront = {"ms_per_spp": round(tw / args.wavefront_spp * 1e3, 3), "spp": args.wavefront_spp,
-                     "form": wform, "Msamples_per_s": round(npix * args.wavefront_spp / tw / 1e6, 3),
-                     "timed": False}
+        bstats = ctx.kernel_stats()
+        # wavefront form: the shadow trace timed alone (on the main stream, not overlapping the
+        # closest-hit trace of the next bounce), for its own roofline
+        if "trace_shadow" in bstats:
+            ctx.reset_stats()
+            ctx.set_option("serial_shadow", 1)
+            ctx.render_device(min(spp, 4), args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
+            torch.cuda.synchronize(dev)
+            iso = ctx.kernel_stats()
+            ctx.set_option("serial_shadow", 0)
+        # untimed same-run leg in the launch-per-stage layout (wavefront: raygen -> closest -> shade -> shadow
+        # -> splat launches per bounce), when the timed render ran a persistent kernel
+        if rank == 0 and args.wavefront_spp > 0 and form["form"] in ("k_path", "k_path_defer", "k_path_spec"):
+            # the wavefront, whatever form the timed render ran; the options in effect before are
+            # restored afterwards
+            saved = {k: ctx.option_set(k) for k in ("stats", "path")}
+            ctx.reset_stats()
+            ctx.set_option("stats", 0)
+            ctx.set_option("path", 0)
+            ctx.render_device(1, args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)   # warm
+            torch.cuda.synchronize(dev)
+            tw = time.perf_counter()
+            ctx.render_device(args.wavefront_spp, args.max_depth, tiles, rad.data_ptr(), wgt.data_ptr(), stream)
+            torch.cuda.synchronize(dev)
+            tw = time.perf_counter() - tw
+            wform = ctx.render_form()["form"]
+            for k, v in saved.items():
+                if v is not None:   # every one of them was set above (bench options / --opt)
+                    ctx.set_option(k, v)
+            wavefront = {"ms_per_spp": round(tw / args.wavefront_spp * 1e3, 3), "spp": args.wavefront_spp,
+                         "form": wform, "Msamples_per_s": round(npix * args.wavefront_spp / tw / 1e6, 3),
+                         "timed": False}
 
     if rank != 0:
         if world > 1:
@@ -671,10 +805,12 @@ def main():
                           "rank_Msamples_per_s": round(npix * spp / elapsed / 1e6, 3), "passes": passes,
                           "projected_node_Msamples_per_s": round(W * H * spp / elapsed / 1e6, 3),
                           "form": form, "wavefront": wavefront,
+                          # --full: the untimed breakdown and counting passes
                           "kernels": {k: {"launches": v["launches"], "avg_ms": round(v["total_ms"] / v["launches"], 4)}
-                                      for k, v in bstats.items()},
+                                      for k, v in bstats.items()} if full else None,
                           "rays_per_pixel": {"closest": counts["per_mode"]["closest"]["rays"] / max(1, npix),
-                                             "shadow": counts["per_mode"]["shadow"]["rays"] / max(1, npix)}}),
+                                             "shadow": counts["per_mode"]["shadow"]["rays"] / max(1, npix)}
+                                            if full else None}),
               flush=True)
         return
     samples = W * H * spp
@@ -689,96 +825,98 @@ def main():
               # the form the library ran (north_star names a wavefront; DESIGN.md §0 / §3.8 give the
               # measured reason for the persistent kernel on this scene) and the wavefront beside it
               "form": form["form"], "ordered_fetch": form["ordered"]}
-    # roofline of the dominant kernel: the persistent path kernel (every closest-hit and shadow ray
-    # of the render, SURVEY.md §8d "t_traversal_kernels"), or the wavefront's closest-hit trace
-    cl = counts["per_mode"]["closest"]
-    sh = counts["per_mode"]["shadow"]
-    ray_bytes = lambda c: RAY_BYTES * c["rays"] + BOX_BYTES * c["box_tests"] + TRI_BYTES * c["tri_tests"]
-    dom = "path" if "path" in cstats else "trace_closest"
-    if dom == "path":   # the counting pass rendered 1 spp; the timed launch renders spp
-        bytes_per_launch = (ray_bytes(cl) + ray_bytes(sh)) * spp
-        prof_name = PATH_KERNEL_PROF_NAME
-    else:
-        bytes_per_launch = ray_bytes(cl) / (cstats.get("trace_closest", {}).get("launches", 0) or 1)
-        prof_name = TRACE_KERNEL_PROF_NAME
-    kc = kstats.get(dom) or bstats[dom]   # timed region (breakdown pass if --timed-stats 0)
-    avg_ms = kc["total_ms"] / kc["launches"]
-    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9
-    # the PMC record of the same kernel from the committed profile of this exact config (the driver's
-    # command, tools/profile_driver.sh); None when no profile of this config exists
-    prof, traffic_src = measured_traffic(prof_name, config, spp=spp if dom == "path" else None)
-    traffic = prof["traffic"] if prof else None
-    # hardware fraction beside the model one: the PMC-measured HBM bytes over the live launch time
-    hbm_achieved = traffic / (avg_ms * 1e-3) / 1e9 if traffic else None
-    # read-only HBM fraction (north_star: "HBM-read roofline"): the L2 -> fabric read bytes, from the
-    # request counts by size, calibrated on the traversal's widths (profiles/r21_fetch_calib.json: every
-    # request is 128 B); Infinity-Cache hits are inside it, so it bounds the HBM reads from above
-    read_traffic = prof.get("read_traffic") if prof else None
-    hbm_read_achieved = read_traffic / (avg_ms * 1e-3) / 1e9 if read_traffic else None
-    l2_bytes = prof.get("l2_bytes") if prof else None
-    l2_achieved = l2_bytes / (avg_ms * 1e-3) / 1e9 if l2_bytes else None
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "hbm_achieved": round(hbm_achieved, 1) if hbm_achieved else None,
-                "hbm_frac": round(hbm_achieved / HBM_PEAK_GBS, 4) if hbm_achieved else None,
-                "hbm_read_achieved": round(hbm_read_achieved, 1) if hbm_read_achieved else None,
-                "hbm_read_frac": round(hbm_read_achieved / HBM_PEAK_GBS, 4) if hbm_read_achieved else None,
-                "read_bytes_source": prof.get("read_bytes_source") if prof else None,
-                "fetch_calibration": "profiles/r21_fetch_calib.json",
-                # L2 request bandwidth of the same launch (TCC_REQ x 128 B, PMC) against the L2 peak
-                "l2_achieved": round(l2_achieved, 1) if l2_achieved else None,
-                "l2_peak": L2_PEAK_GBS,
-                "l2_frac": round(l2_achieved / L2_PEAK_GBS, 4) if l2_achieved else None,
-                "rays_per_sample": {"closest": cl["rays"] / max(1, npix), "shadow": sh["rays"] / max(1, npix)},
-                "kernel": dom, "bytes_per_launch": bytes_per_launch, "avg_launch_ms": avg_ms,
-                "per_ray": {"box_tests": cl["box_tests"] / max(1, cl["rays"]),
-                            "node_visits": cl["visits"] / max(1, cl["rays"]),
-                            "leaf_tests": cl["leaf_tests"] / max(1, cl["rays"]),
-                            "tri_tests": cl["tri_tests"] / max(1, cl["rays"])},
-                "shadow_per_ray": {"box_tests": sh["box_tests"] / max(1, sh["rays"]),
-                                   "node_visits": sh["visits"] / max(1, sh["rays"]),
-                                   "leaf_tests": sh["leaf_tests"] / max(1, sh["rays"]),
-                                   "tri_tests": sh["tri_tests"] / max(1, sh["rays"])},
-                # SIMD lane utilisation of the traversal loop (node visits per lane slot) and of
-                # the triangle loop (triangle tests per lane slot), from the counting pass; the path
-                # kernel runs both ray kinds in one loop (its slots are counted with the closest set)
-                "lane_util": ({"path": {"traversal": (cl["visits"] + sh["visits"]) / max(1, cl["slots_traversal"]),
-                                        "holding_ray": cl["slots_busy"] / max(1, cl["slots_traversal"]),
-                                        "triangles": (cl["tri_tests"] + sh["tri_tests"]) / max(1, cl["slots_tri"])}}
-                              if dom == "path" else
-                              {m: {"traversal": c["visits"] / max(1, c["slots_traversal"]),
-                                   "holding_ray": c["slots_busy"] / max(1, c["slots_traversal"]),
-                                   "triangles": c["tri_tests"] / max(1, c["slots_tri"])}
-                               for m, c in (("closest", cl), ("shadow", sh))})}
-    if dom == "path" and prof:
-        roofline["latency"] = latency_model(prof, cl, sh, npix, value * 1e6)
-    if dom == "path":
-        roofline["time_split"] = time_split(pprof, counts)
-    if lines:
-        # the fabric's reads per sample pass against the distinct lines a pass touches: how often a line
-        # is fetched again within a pass
-        distinct = 128 * sum(lines.values())
-        fabric = read_traffic / spp if (read_traffic and dom == "path") else None
-        roofline["lines_per_pass"] = {**{k + "_gb": round(128 * v / 1e9, 4) for k, v in lines.items()},
-                                      "distinct_gb": round(distinct / 1e9, 4),
-                                      "fabric_read_gb": round(fabric / 1e9, 4) if fabric else None,
-                                      "fabric_over_distinct": round(fabric / distinct, 2) if fabric and distinct else None,
-                                      "source": "counting build, untimed 1-spp k_path pass, bitmap of 128-B lines"}
-    if achieved > HBM_PEAK_GBS:   # the model bytes are not HBM bytes: caches serve most of them
-        roofline["note"] = ("the SURVEY.md §8d algorithmic bytes exceed the HBM peak: most node and triangle reads "
-                            "hit L2 or the Infinity Cache (on C3 ~66 % L2 hits by PMC, profiles/r20g_summary.md; a small scene's BVH is wholly "
-                            "cache-resident), so frac is a model figure; hbm_frac is the HBM traffic measured by PMC "
-                            "over the same launch time")
-    if iso and "trace_shadow" in iso:   # the shadow trace alone: its own roofline (wavefront form)
-        ks = iso["trace_shadow"]
-        sms = ks["total_ms"] / ks["launches"]
-        sb = ray_bytes(sh) / (cstats.get("trace_shadow", {}).get("launches", 0) or 1)
-        roofline["shadow_isolated"] = {"kernel": "trace_shadow", "avg_launch_ms": sms, "bytes_per_launch": sb,
-                                       "achieved": round(sb / (sms * 1e-3) / 1e9, 1),
-                                       "frac": round(sb / (sms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                       "closest_isolated_ms": iso["trace_closest"]["total_ms"] / iso["trace_closest"]["launches"]}
+    roofline = None
+    if full:
+        # roofline of the dominant kernel: the persistent path kernel (every closest-hit and shadow ray
+        # of the render, SURVEY.md §8d "t_traversal_kernels"), or the wavefront's closest-hit trace
+        cl = counts["per_mode"]["closest"]
+        sh = counts["per_mode"]["shadow"]
+        ray_bytes = lambda c: RAY_BYTES * c["rays"] + BOX_BYTES * c["box_tests"] + TRI_BYTES * c["tri_tests"]
+        dom = "path" if "path" in cstats else "trace_closest"
+        if dom == "path":   # the counting pass rendered 1 spp; the timed launch renders spp
+            bytes_per_launch = (ray_bytes(cl) + ray_bytes(sh)) * spp
+            prof_name = PATH_KERNEL_PROF_NAME
+        else:
+            bytes_per_launch = ray_bytes(cl) / (cstats.get("trace_closest", {}).get("launches", 0) or 1)
+            prof_name = TRACE_KERNEL_PROF_NAME
+        kc = kstats.get(dom) or bstats[dom]   # timed region (breakdown pass if --timed-stats 0)
+        avg_ms = kc["total_ms"] / kc["launches"]
+        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9
+        # the PMC record of the same kernel from the committed profile of this exact config (the driver's
+        # command, tools/profile_driver.sh); None when no profile of this config exists
+        prof, traffic_src = measured_traffic(prof_name, config, spp=spp if dom == "path" else None)
+        traffic = prof["traffic"] if prof else None
+        # hardware fraction beside the model one: the PMC-measured HBM bytes over the live launch time
+        hbm_achieved = traffic / (avg_ms * 1e-3) / 1e9 if traffic else None
+        # read-only HBM fraction (the HBM-read roofline): the L2 -> fabric read bytes, from the
+        # request counts by size, calibrated on the traversal's widths (profiles/r21_fetch_calib.json: every
+        # request is 128 B); Infinity-Cache hits are inside it, so it bounds the HBM reads from above
+        read_traffic = prof.get("read_traffic") if prof else None
+        hbm_read_achieved = read_traffic / (avg_ms * 1e-3) / 1e9 if read_traffic else None
+        l2_bytes = prof.get("l2_bytes") if prof else None
+        l2_achieved = l2_bytes / (avg_ms * 1e-3) / 1e9 if l2_bytes else None
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "hbm_achieved": round(hbm_achieved, 1) if hbm_achieved else None,
+                    "hbm_frac": round(hbm_achieved / HBM_PEAK_GBS, 4) if hbm_achieved else None,
+                    "hbm_read_achieved": round(hbm_read_achieved, 1) if hbm_read_achieved else None,
+                    "hbm_read_frac": round(hbm_read_achieved / HBM_PEAK_GBS, 4) if hbm_read_achieved else None,
+                    "read_bytes_source": prof.get("read_bytes_source") if prof else None,
+                    "fetch_calibration": "profiles/r21_fetch_calib.json",
+                    # L2 request bandwidth of the same launch (TCC_REQ x 128 B, PMC) against the L2 peak
+                    "l2_achieved": round(l2_achieved, 1) if l2_achieved else None,
+                    "l2_peak": L2_PEAK_GBS,
+                    "l2_frac": round(l2_achieved / L2_PEAK_GBS, 4) if l2_achieved else None,
+                    "rays_per_sample": {"closest": cl["rays"] / max(1, npix), "shadow": sh["rays"] / max(1, npix)},
+                    "kernel": dom, "bytes_per_launch": bytes_per_launch, "avg_launch_ms": avg_ms,
+                    "per_ray": {"box_tests": cl["box_tests"] / max(1, cl["rays"]),
+                                "node_visits": cl["visits"] / max(1, cl["rays"]),
+                                "leaf_tests": cl["leaf_tests"] / max(1, cl["rays"]),
+                                "tri_tests": cl["tri_tests"] / max(1, cl["rays"])},
+                    "shadow_per_ray": {"box_tests": sh["box_tests"] / max(1, sh["rays"]),
+                                       "node_visits": sh["visits"] / max(1, sh["rays"]),
+                                       "leaf_tests": sh["leaf_tests"] / max(1, sh["rays"]),
+                                       "tri_tests": sh["tri_tests"] / max(1, sh["rays"])},
+                    # SIMD lane utilisation of the traversal loop (node visits per lane slot) and of
+                    # the triangle loop (triangle tests per lane slot), from the counting pass; the path
+                    # kernel runs both ray kinds in one loop (its slots are counted with the closest set)
+                    "lane_util": ({"path": {"traversal": (cl["visits"] + sh["visits"]) / max(1, cl["slots_traversal"]),
+                                            "holding_ray": cl["slots_busy"] / max(1, cl["slots_traversal"]),
+                                            "triangles": (cl["tri_tests"] + sh["tri_tests"]) / max(1, cl["slots_tri"])}}
+                                  if dom == "path" else
+                                  {m: {"traversal": c["visits"] / max(1, c["slots_traversal"]),
+                                       "holding_ray": c["slots_busy"] / max(1, c["slots_traversal"]),
+                                       "triangles": c["tri_tests"] / max(1, c["slots_tri"])}
+                                   for m, c in (("closest", cl), ("shadow", sh))})}
+        if dom == "path" and prof:
+            roofline["latency"] = latency_model(prof, cl, sh, npix, value * 1e6)
+        if dom == "path":
+            roofline["time_split"] = time_split(pprof, counts)
+        if lines:
+            # the fabric's reads per sample pass against the distinct lines a pass touches: how often a line
+            # is fetched again within a pass
+            distinct = 128 * sum(lines.values())
+            fabric = read_traffic / spp if (read_traffic and dom == "path") else None
+            roofline["lines_per_pass"] = {**{k + "_gb": round(128 * v / 1e9, 4) for k, v in lines.items()},
+                                          "distinct_gb": round(distinct / 1e9, 4),
+                                          "fabric_read_gb": round(fabric / 1e9, 4) if fabric else None,
+                                          "fabric_over_distinct": round(fabric / distinct, 2) if fabric and distinct else None,
+                                          "source": "counting build, untimed 1-spp k_path pass, bitmap of 128-B lines"}
+        if achieved > HBM_PEAK_GBS:   # the model bytes are not HBM bytes: caches serve most of them
+            roofline["note"] = ("the SURVEY.md §8d algorithmic bytes exceed the HBM peak: most node and triangle reads "
+                                "hit L2 or the Infinity Cache (on C3 ~66 % L2 hits by PMC, profiles/r20g_summary.md; a small scene's BVH is wholly "
+                                "cache-resident), so frac is a model figure; hbm_frac is the HBM traffic measured by PMC "
+                                "over the same launch time")
+        if iso and "trace_shadow" in iso:   # the shadow trace alone: its own roofline (wavefront form)
+            ks = iso["trace_shadow"]
+            sms = ks["total_ms"] / ks["launches"]
+            sb = ray_bytes(sh) / (cstats.get("trace_shadow", {}).get("launches", 0) or 1)
+            roofline["shadow_isolated"] = {"kernel": "trace_shadow", "avg_launch_ms": sms, "bytes_per_launch": sb,
+                                           "achieved": round(sb / (sms * 1e-3) / 1e9, 1),
+                                           "frac": round(sb / (sms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                           "closest_isolated_ms": iso["trace_closest"]["total_ms"] / iso["trace_closest"]["launches"]}
     cpu = None
-    if args.cpu_baseline and world == 1:
+    if full and args.cpu_baseline and world == 1:
         sys.path.insert(0, str(ROOT / "oracle"))
         import py_oracle
         nodes, tris = ctx.accel_export()
@@ -801,7 +939,7 @@ def main():
                "value_tight_cull": round(cpx * args.cpu_spp / dt_tight / 1e6, 4)}
 
     configs = None
-    if args.side_legs and world == 1 and args.scene == "soup":
+    if full and args.side_legs and world == 1 and args.scene == "soup":
         side_kw = dict(build_kw)
         configs = {}
         for name in SIDE_LEGS:
@@ -820,6 +958,8 @@ def main():
         "data": ("synthetic; REHEARSAL: the ranks shared one GPU and gathered over gloo, not a measurement"
                  if rehearse else "synthetic"),
         "config": config,
+        # null without --full: wavefront, roofline, cpu_baseline, configs and kernels take runs of their own
+        "full": full,
         "wavefront_ms_per_spp": wavefront["ms_per_spp"] if wavefront else None,
         "wavefront": wavefront,
         "roofline": roofline, "cpu_baseline": cpu, "frame_check": frame_check,
@@ -827,9 +967,9 @@ def main():
         # per-kernel averages from an untimed pass with events on every launch (the timed region
         # times trace_closest only: events around every launch cost ~7 % at an 8-way rank)
         "kernels": {k: {"launches": v["launches"], "avg_ms": round(v["total_ms"] / v["launches"], 4)}
-                    for k, v in bstats.items()},
-        "bvh": {"nodes": info.n_nodes, "depth": info.max_depth, "build_s": round(info.build_ms / 1e3, 2),
-                "setup_s": round(t_setup, 2), "build_threads": build_threads},
+                    for k, v in bstats.items()} if full else None,
+        "bvh": {"nodes": info.n_nodes, "depth": info.max_depth, "build_s": round(build_ms / 1e3, 2),
+                "cached": bool(cached), "setup_s": round(t_setup, 2), "build_threads": build_threads},
     }
     print(json.dumps(line), flush=True)
     if world > 1:

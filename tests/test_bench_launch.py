@@ -165,3 +165,69 @@ def test_bvh_share_falls_back_when_shm_has_no_room(tmp_path):
                                   [str(tmp_path / "missing2")]), nprocs=2, join=True)
     assert (out2 / "r0").read_text() == "built|build"
     assert (out2 / "r1").read_text() == "built|build"
+
+
+def test_dump_outputs_whole_film_and_seeded_sample(tmp_path):
+    """--dump-outputs: a film within the limit is written whole (f32, the ranks' parts one after the
+    other); a larger one is cut to the same seeded sample of its pixels every time, named by
+    pixel_index.npy, and the files stay within the limit."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    parts = [(rng.random((n, 3), dtype=np.float32), np.full(n, 7.0, np.float32)) for n in (1000, 900)]
+    bench.dump_outputs(tmp_path / "whole", parts)
+    rad, wgt = np.load(tmp_path / "whole" / "radiance.npy"), np.load(tmp_path / "whole" / "weight.npy")
+    assert rad.dtype == np.float32 and wgt.dtype == np.float32
+    assert np.array_equal(rad, np.concatenate([p[0] for p in parts])) and wgt.shape == (1900,)
+    assert not (tmp_path / "whole" / "pixel_index.npy").exists()
+    limit = 24 * 500
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, parts, limit_bytes=limit)
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 500 and len(set(idx.tolist())) == 500
+    assert np.array_equal(np.load(tmp_path / "a" / "radiance.npy"), rad[idx.astype(np.int64)])
+    for f in ("radiance.npy", "weight.npy", "pixel_index.npy"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    payload = sum(np.load(tmp_path / "a" / f).nbytes for f in ("radiance.npy", "weight.npy", "pixel_index.npy"))
+    assert payload <= limit
+
+
+def test_bvh_cache_prepared_once_and_keyed(tmp_path, monkeypatch):
+    """bench.py --prepare-cache (build()): the run's BVH2, built on the host by the product builder with
+    the run's parameters, lands in the user's cache directory once, only where a GPU is visible, keyed
+    by the scene and the build parameters; small scenes and the GPU builder have no entry."""
+    import argparse
+    import numpy as np
+    from akari_amd import capi, scene
+    monkeypatch.setenv("XDG_CACHE_HOME", str(tmp_path))
+    monkeypatch.setattr(bench, "BVH_CACHE_MIN_TRIS", 1000)
+    args = argparse.Namespace(scene="soup", tris=3000, leaf=4, sah_isect=4.0, bins=32, builder="sbvh",
+                              spatial_budget=0.0)
+    kw, threads = bench.build_params(args, capi, 1)
+    assert kw["n_threads"] == threads and kw["builder"] == capi.BUILDER_SBVH
+    base = bench.bvh_cache_base(args, kw, capi)
+    assert base.parent == tmp_path / "akari_amd"
+    assert bench.bvh_cache_base(argparse.Namespace(**{**vars(args), "tris": 999}), kw, capi) is None
+    assert bench.bvh_cache_base(argparse.Namespace(**{**vars(args), "builder": "lbvh"}), kw, capi) is None
+    assert bench.bvh_cache_base(argparse.Namespace(**{**vars(args), "tris": 3001}), kw, capi) != base
+    assert bench.bvh_cache_base(args, dict(kw, max_leaf_size=2), capi) != base
+    monkeypatch.setattr(bench, "visible_gpu_count", lambda *a, **k: 0)
+    bench.prepare_cache(args)
+    assert bench.load_cached_bvh(base) is None and not list(tmp_path.iterdir())
+    monkeypatch.setattr(bench, "visible_gpu_count", lambda *a, **k: 1)
+    bench.prepare_cache(args)
+    nodes, tris, meta = bench.load_cached_bvh(base)
+    cs = scene.compile_scene(scene.soup_scene(n_tris=3000))
+    n0, t0, info = capi.build_bvh_host(cs.vertices, cs.indices, **kw)
+    assert nodes.tobytes() == n0.tobytes() and tris.tobytes() == t0.tobytes()
+    assert meta["n_nodes"] == info.n_nodes and meta["sah_cost"] == info.sah_cost
+    left = sorted(p.name for p in base.parent.iterdir())
+    assert left == sorted(base.name + s for s in (".json", "_nodes.npy", "_tris.npy"))
+    stamp = Path(f"{base}.json").stat().st_mtime_ns
+    bench.prepare_cache(args)                       # a complete entry is left alone
+    assert Path(f"{base}.json").stat().st_mtime_ns == stamp
+    Path(f"{base}.json").write_text('{"n_nodes": 1}')   # figures missing: no entry, no exception
+    assert bench.load_cached_bvh(base) is None
+    Path(f"{base}.json").write_text(json.dumps(meta))
+    assert bench.load_cached_bvh(base) is not None
+    Path(f"{base}_tris.npy").unlink()               # an incomplete one is no entry
+    assert bench.load_cached_bvh(base) is None

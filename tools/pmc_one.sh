@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 out=gpurun_out/pmc1_$name
 mkdir -p "$out"
 timeout -k 10 240 rocprofv3 --pmc $counters --kernel-trace --output-format csv -d "$out" -o run -- \
-    python3 bench.py $args > "$out/bench.log" 2>&1
+    python3 bench.py --full $args > "$out/bench.log" 2>&1
 rc=$?
 echo "pmc $name rc=$rc"
 exit $rc

@@ -14,7 +14,7 @@ run() {  # name, counters...
     local name=$1; shift
     echo "pass $name: $*" | tee -a "$out/progress.txt"
     timeout -k 10 200 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$out/$name" -o run -- \
-        python3 bench.py $args > "$out/$name.log" 2>&1
+        python3 bench.py --full $args > "$out/$name.log" 2>&1
     local rc=$?
     echo "pass $name rc=$rc" | tee -a "$out/progress.txt"
     return $rc

@@ -20,7 +20,7 @@ for set in \
   i=$((i+1))
   echo "pass $i: $set" | tee -a "$out/progress.txt"
   timeout -k 10 150 rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$out/p$i" -o run -- \
-      python3 bench.py $args > "$out/p$i.log" 2>&1
+      python3 bench.py --full $args > "$out/p$i.log" 2>&1
   rc=$?
   echo "pass $i rc=$rc" | tee -a "$out/progress.txt"
   if [ $rc -ne 0 ]; then exit $rc; fi

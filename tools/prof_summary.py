@@ -63,7 +63,7 @@ def main(tag):
     dst = ROOT / "profiles"
     dst.mkdir(exist_ok=True)
     args = (src / "args.txt").read_text().strip() if (src / "args.txt").exists() else "(tools/profile.sh)"
-    out = [f"# rocprofv3 summary — {tag}", "", f"Command: `python3 bench.py {args}` under rocprofv3 "
+    out = [f"# rocprofv3 summary — {tag}", "", f"Command: `python3 bench.py --full {args}` under rocprofv3 "
            f"(`tools/profile_driver.sh {tag}`: one pass per counter group, `--kernel-trace` only beside them).", ""]
     ks = list(csv.DictReader(open(src / "kt" / "run_kernel_stats.csv")))
     out += ["## Kernel time (`rocprofv3 --kernel-trace --stats`)", "",
@@ -175,7 +175,7 @@ def main(tag):
             out.append(f"- L2 -> fabric read requests: {c['TCC_EA0_RDREQ_sum']:.3g}, mean in flight x time / count = "
                        f"{c['TCC_EA0_RDREQ_LEVEL_sum'] / c['TCC_EA0_RDREQ_sum']:.0f} cycles per request")
     (dst / f"{tag}_traffic.json").write_text(json.dumps(
-        {"tag": tag, "command": f"python3 bench.py {args}", "workload": workload,
+        {"tag": tag, "command": f"python3 bench.py --full {args}", "workload": workload,
          "source": f"rocprofv3 passes of tools/profile_driver.sh {tag} (the raw counter csvs stay under gpurun_out/; "
                    "the per-launch counters the summary uses are in this file)", "kernels": kernels}, indent=1) + "\n")
     (dst / f"{tag}_summary.md").write_text("\n".join(out) + "\n")

@@ -12,11 +12,11 @@ out=gpurun_out/prof_$tag
 mkdir -p "$out"
 set -o pipefail
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -o run -- \
-    python3 bench.py $args > "$out/kt.log" 2>&1 || exit $?
+    python3 bench.py --full $args > "$out/kt.log" 2>&1 || exit $?
 timeout -k 10 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmc_fetch" -o run -- \
-    python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 > "$out/pmc_fetch.log" 2>&1 || exit $?
+    python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 > "$out/pmc_fetch.log" 2>&1 || exit $?
 timeout -k 10 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/pmc_write" -o run -- \
-    python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 > "$out/pmc_write.log" 2>&1 || exit $?
+    python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 > "$out/pmc_write.log" 2>&1 || exit $?
 timeout -k 10 900 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d "$out/pmc_tcc" -o run -- \
-    python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 > "$out/pmc_tcc.log" 2>&1 || exit $?
+    python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 > "$out/pmc_tcc.log" 2>&1 || exit $?
 echo "profile $tag done"

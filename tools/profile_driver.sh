@@ -45,10 +45,10 @@ for name in $passes; do
     echo "pass $name" | tee -a "$out/progress.txt"
     if [ "$name" = kt ]; then
         timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -o run -- \
-            python3 bench.py $args > "$out/kt.log" 2>&1
+            python3 bench.py --full $args > "$out/kt.log" 2>&1
     else
         timeout -s KILL 240 rocprofv3 --pmc ${PMC[$name]} --kernel-trace --output-format csv -d "$out/$name" -o run -- \
-            python3 bench.py $args --cpu-baseline 0 --side-legs 0 --wavefront-spp 0 > "$out/$name.log" 2>&1
+            python3 bench.py --full $args --cpu-baseline 0 --side-legs 0 --wavefront-spp 0 > "$out/$name.log" 2>&1
     fi
     rc=$?
     echo "pass $name rc=$rc" | tee -a "$out/progress.txt"

@@ -10,6 +10,6 @@ for lib in "$@"; do
     mkdir -p "$out"
     echo "pass $name"
     AKR_HIP_LIB=$PWD/$lib timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out" -o run -- \
-        python3 bench.py --steps 20 --warmup 5 --cpu-baseline 0 --side-legs 0 --wavefront-spp 0 > "$out/bench.log" 2>&1 || exit $?
+        python3 bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --side-legs 0 --wavefront-spp 0 > "$out/bench.log" 2>&1 || exit $?
 done
 echo "write_ab $tag done"
