@@ -101,6 +101,13 @@ class PixelProbe(C.Structure):
     _fields_ = [("seed", C.c_uint32), ("closest_rays", C.c_uint32), ("shadow_rays", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class RenderStateInfo(C.Structure):
+    _fields_ = [("n_pixels", C.c_uint64), ("spp_done", C.c_int32), ("max_depth", C.c_int32),
+                ("ray_clamp", C.c_float), ("flags", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("n_tiles", C.c_int32), ("_pad", C.c_int32)]
+
+
+MAX_SESSION_SPP = 1 << 24   # a slot's weight is an f32 count of its samples
 TEX_CONSTANT, TEX_IMAGE = 0, 1
 PT_EXACT_CULL = 1
 BUILDER_SAH, BUILDER_LBVH, BUILDER_SBVH = 0, 1, 2
@@ -172,6 +179,11 @@ EXPORTS = {
     "akr_bvh_host_wide": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "akr_bvh_host_wide_nodes": (_P, [_P]),
     "akr_bvh_host_wide_leaves": (_P, [_P]),
+    "akr_hip_render_continue": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "akr_hip_render_continue_device": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "akr_hip_render_state_info": (C.c_int, [_P, C.POINTER(RenderStateInfo)]),
+    "akr_hip_render_state_export": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "akr_hip_render_state_import": (C.c_int, [_P, C.POINTER(PtParams), _P, C.c_int32, _P, _P, C.c_uint64]),
 }
 
 _lib = None
@@ -452,6 +464,51 @@ class HipContext:
                                                    C.c_void_p(d_radiance), C.c_void_p(d_weight), C.c_void_p(stream),
                                                    C.byref(npx)))
         return npx.value
+
+    # ---- render sessions (include/akr_hip.h): the last path render, continued
+
+    def render_continue(self, spp, width, height, radiance=None, weight=None):
+        """`spp` more samples per slot of the context's session; the session's totals are added to the
+        full-frame host buffers (fresh zeroed ones by default, which then hold the film)."""
+        if radiance is None:
+            radiance = np.zeros((height, width, 3), np.float32)
+        if weight is None:
+            weight = np.zeros((height, width), np.float32)
+        assert radiance.dtype == np.float32 and radiance.flags.c_contiguous and radiance.size == 3 * width * height
+        assert weight.dtype == np.float32 and weight.flags.c_contiguous and weight.size == width * height
+        self._check(self.lib.akr_hip_render_continue(self.h, int(spp), _ptr(radiance), _ptr(weight)))
+        return radiance, weight
+
+    def render_continue_device(self, spp, d_radiance: int, d_weight: int, stream: int = 0):
+        """Device form: the session's totals overwrite packed device buffers; returns the slot count."""
+        npx = C.c_uint64(0)
+        self._check(self.lib.akr_hip_render_continue_device(self.h, int(spp), C.c_void_p(d_radiance),
+                                                            C.c_void_p(d_weight), C.c_void_p(stream), C.byref(npx)))
+        return npx.value
+
+    def render_state_info(self) -> dict:
+        info = RenderStateInfo()
+        self._check(self.lib.akr_hip_render_state_info(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in RenderStateInfo._fields_ if k != "_pad"}
+
+    def render_state_export(self):
+        """The session's (sampler uint32[n], film float32[n, 4]) in packed tile order."""
+        n = self.render_state_info()["n_pixels"]
+        sampler = np.zeros(n, np.uint32)
+        film = np.zeros((n, 4), np.float32)
+        self._check(self.lib.akr_hip_render_state_export(self.h, _ptr(sampler), _ptr(film), n))
+        return sampler, film
+
+    def render_state_import(self, spp, max_depth, tiles, sampler, film, ray_clamp=0.0, exact_cull=False):
+        """Establish a session as if `spp` samples had just been rendered over `tiles`."""
+        sampler = np.ascontiguousarray(sampler, np.uint32).reshape(-1)
+        film = np.ascontiguousarray(film, np.float32).reshape(-1)
+        if film.size != 4 * sampler.size:
+            raise ValueError("film must hold four floats per sampler state")
+        p = PtParams(int(spp), int(max_depth), float(ray_clamp), PT_EXACT_CULL if exact_cull else 0)
+        arr, n = self._rects(tiles)
+        self._check(self.lib.akr_hip_render_state_import(self.h, C.byref(p), _arr_ptr(arr), n, _ptr(sampler),
+                                                         _ptr(film), sampler.size))
 
     def ray_steps(self, n: int) -> np.ndarray:
         """Per-ray traversal iterations of the last standalone trace (option "ray_steps")."""

@@ -10,6 +10,10 @@ its CPU AO adds every sample with weight 1 (cpu/integrator.cpp:78); both resolve
 image acc/spp, and this film holds the CPU form (radiance = acc, weight = spp).
 
 Usage: python -m akari_amd.render scene.akari [--out image.png|.pfm] [--gpus N]
+       ... [--pass-spp N] [--preview] [--time-budget SECONDS] [--checkpoint FILE] [--resume FILE]
+The second line renders a Path scene on one GPU in passes (akari_amd/progressive.py): the output is
+rewritten after each pass, the render stops after the pass that exceeds the budget, the session is
+saved after each pass, or a saved one is continued up to the scene's spp.
 """
 from __future__ import annotations
 
@@ -17,11 +21,12 @@ import argparse
 import math
 import sys
 import time
+from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import capi, film, scene
+from . import capi, film, progressive, scene
 from .dist import tile_grid
 
 
@@ -54,6 +59,45 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), **build_kw) -> 
             c.close()
 
 
+def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optional[int] = None,
+                             on_pass=None, time_budget: Optional[float] = None, checkpoint=None, resume=None,
+                             **build_kw) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Render a Path scene in passes on one device; returns (radiance, weight, spp_done).
+
+    pass_spp: samples per pass (default: each pass doubles the samples done); on_pass(spp_done,
+    radiance, weight) after each pass; checkpoint: file the session is saved to after each pass;
+    resume: checkpoint file whose session is continued up to the integrator's spp."""
+    it = sc.integrator
+    if not isinstance(it, scene.PathIntegrator):
+        raise ValueError("progressive rendering needs the Path integrator")
+    ck = progressive.Checkpoint.load(resume) if resume is not None else None
+    cs = scene.compile_scene(sc)
+    w, h = (int(v) for v in sc.camera.resolution)
+    tiles = _tiles(sc, it.tile_size)
+    if ck is not None:  # checked before a device is touched
+        ck.check(cs, tiles, w, h)
+        if ck.max_depth != it.max_depth or ck.ray_clamp != float(np.float32(it.ray_clamp)) or ck.flags != 0:
+            raise progressive.CheckpointError(
+                f"checkpoint was rendered with max_depth {ck.max_depth}, ray_clamp {ck.ray_clamp}, flags {ck.flags}; "
+                f"the scene asks for max_depth {it.max_depth}, ray_clamp {it.ray_clamp}")
+        if ck.spp_done > it.spp:
+            raise progressive.CheckpointError(f"checkpoint holds {ck.spp_done} spp, more than the {it.spp} asked for")
+    with capi.HipContext(device) as ctx:
+        scene.upload_scene(ctx, cs, **build_kw)
+        if ck is not None:
+            ck.restore(ctx, cs, tiles)
+
+        def each_pass(done, rad, wt):
+            if checkpoint is not None:
+                progressive.Checkpoint.capture(ctx, cs, tiles).save(checkpoint)
+            return on_pass(done, rad, wt) if on_pass is not None else None
+
+        return progressive.render_progressive(ctx, it.spp, it.max_depth, tiles, w, h,
+                                              schedule=pass_spp if pass_spp is not None else "double",
+                                              on_pass=each_pass, time_budget=time_budget, ray_clamp=it.ray_clamp,
+                                              resume=ck is not None)
+
+
 def write_film(path: str, radiance: np.ndarray, weight: np.ndarray) -> None:
     """Film::write_image (core/film.h:97-113): PNG is sRGB 8-bit, PFM keeps linear floats."""
     if path.lower().endswith(".pfm"):
@@ -68,16 +112,51 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--out", default=None, help="output image (default: the scene's `output` field)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--spp", type=int, default=None, help="override the integrator's spp")
+    ap.add_argument("--pass-spp", type=int, default=None, metavar="N",
+                    help="render in passes of N samples (default with the options below: each pass doubles the samples)")
+    ap.add_argument("--preview", action="store_true", help="rewrite the output after each pass")
+    ap.add_argument("--time-budget", type=float, default=None, metavar="SECONDS",
+                    help="stop after the first pass that ends past this many seconds of rendering")
+    ap.add_argument("--checkpoint", default=None, metavar="FILE", help="save the render session after each pass")
+    ap.add_argument("--resume", default=None, metavar="FILE", help="continue a saved session up to the scene's spp")
     args = ap.parse_args(argv)
+    passes = (args.pass_spp is not None or args.preview or args.time_budget is not None or
+              args.checkpoint is not None or args.resume is not None)
+    if passes:  # checked before the scene is uploaded: no device is needed to refuse these
+        if args.gpus != 1:
+            ap.error("--pass-spp, --preview, --time-budget, --checkpoint and --resume render on one GPU (--gpus 1)")
+        if args.pass_spp is not None and args.pass_spp < 1:
+            ap.error("--pass-spp needs at least one sample per pass")
+        if args.time_budget is not None and not args.time_budget > 0:
+            ap.error("--time-budget needs a positive number of seconds")
+        if args.resume is not None and not Path(args.resume).is_file():
+            ap.error(f"--resume: no checkpoint file {args.resume}")
     sc = scene.load_scene_file(args.scene)
     if args.spp is not None:
         sc.integrator.spp = args.spp
-    t0 = time.time()
-    rad, wt = render_scene(sc, devices=list(range(args.gpus)))
+    if passes and not isinstance(sc.integrator, scene.PathIntegrator):
+        ap.error(f"--pass-spp, --preview, --time-budget, --checkpoint and --resume need the Path integrator; "
+                 f"the scene's is {type(sc.integrator).__name__}")
     out = args.out or sc.output
+    t0 = time.time()
+    if passes:
+        def show(done, rad, wt):
+            if args.preview:
+                write_film(out, rad, wt)
+                print(f"pass to {done} spp: {time.time() - t0:.2f}s -> {out}", flush=True)
+
+        try:
+            rad, wt, done = render_scene_progressive(sc, 0, pass_spp=args.pass_spp, on_pass=show,
+                                                     time_budget=args.time_budget, checkpoint=args.checkpoint,
+                                                     resume=args.resume)
+        except progressive.CheckpointError as e:
+            ap.error(str(e))
+    else:
+        rad, wt = render_scene(sc, devices=list(range(args.gpus)))
+        done = sc.integrator.spp
     write_film(out, rad, wt)
     print(f"{type(sc.integrator).__name__} {sc.camera.resolution[0]}x{sc.camera.resolution[1]} "
-          f"spp {sc.integrator.spp}: {time.time() - t0:.2f}s -> {out}")
+          f"spp {done}: {time.time() - t0:.2f}s -> {out}")
     return 0
 
 

@@ -237,6 +237,50 @@ class HipPathTracer {
               "render");
     }
 
+    // Render sessions (include/akr_hip.h): the accelerator's context remembers its last render(), and
+    // render_continue adds `more` samples per pixel from where it stopped; the film is cleared and then
+    // holds the session's totals, bit for bit the film of one render() of all the samples.
+    void render_continue(const HipAccelerator &scene, int more, Film &film) const {
+        std::fill(film.radiance.begin(), film.radiance.end(), 0.0f);
+        std::fill(film.weight.begin(), film.weight.end(), 0.0f);
+        check(scene.handle(), akr_hip_render_continue(scene.handle(), more, film.radiance.data(), film.weight.data()),
+              "render_continue");
+    }
+    // the totals into packed device buffers (radiance[3n], weight[n]) on `stream`; returns the slot count
+    uint64_t render_continue_device(const HipAccelerator &scene, int more, float *d_radiance, float *d_weight,
+                                    void *stream = nullptr) const {
+        uint64_t n = 0;
+        check(scene.handle(), akr_hip_render_continue_device(scene.handle(), more, d_radiance, d_weight, stream, &n),
+              "render_continue_device");
+        return n;
+    }
+    akr_render_state_info render_state_info(const HipAccelerator &scene) const {
+        akr_render_state_info i;
+        check(scene.handle(), akr_hip_render_state_info(scene.handle(), &i), "render_state_info");
+        return i;
+    }
+    // the session's sampler states [n] and film sums [4n] (r, g, b, weight), packed tile order
+    void render_state_export(const HipAccelerator &scene, std::vector<uint32_t> &sampler, std::vector<float> &sums) const {
+        const uint64_t n = render_state_info(scene).n_pixels;
+        sampler.resize(n);
+        sums.resize(4 * n);
+        check(scene.handle(), akr_hip_render_state_export(scene.handle(), sampler.data(), sums.data(), n),
+              "render_state_export");
+    }
+    // a session as if spp_done samples of this tracer had been rendered over a width x height film
+    void render_state_import(const HipAccelerator &scene, int width, int height, int spp_done,
+                             const std::vector<uint32_t> &sampler, const std::vector<float> &sums) const {
+        if (sums.size() != 4 * sampler.size()) throw std::runtime_error("render_state_import: four sums per sampler state");
+        std::vector<akr_rect> tiles;
+        for (int y = 0; y < height; y += tile_size)
+            for (int x = 0; x < width; x += tile_size) tiles.push_back({x, y, x + tile_size, y + tile_size});
+        akr_pt_params p{spp_done, max_depth, ray_clamp, 0};
+        check(scene.handle(),
+              akr_hip_render_state_import(scene.handle(), &p, tiles.data(), (int32_t)tiles.size(), sampler.data(),
+                                          sums.data(), sampler.size()),
+              "render_state_import");
+    }
+
     // Multi-GPU in one process (akr_hip_render_node): tile j on accelerators[j % n], one per device,
     // each built from the same scene; the merged film equals render() on one of them.
     void render_node(const std::vector<const HipAccelerator *> &accels, Film &film) const {

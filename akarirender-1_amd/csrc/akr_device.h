@@ -295,6 +295,10 @@ struct PathArgs {
     uint32_t *lines;               // counting build, k_path, option "count_lines": bitmap of the 128-B lines
     uint32_t lines_span[4];        // read; bit ranges [span[r], span[r + 1]) of the wide nodes, the leaf blob
                                    // and the shading records
+    const uint32_t *state_in;      // per slot, a continued render: the sampler state after the
+                                   // slot's last sample, and `film` holds its sums; null: a fresh render, whose
+                                   // slots start from x + y * width and a zero film
+    uint32_t *state_out;           // per slot: the sampler state after the slot's last sample of this launch
 };
 
 }  // namespace akr

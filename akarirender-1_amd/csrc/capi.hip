@@ -222,6 +222,32 @@ struct akr_hip_ctx {
     std::vector<uint4> h_tiles;
     uint64_t n_pix_last = 0;
     DBuf<uint4> d_tiles;
+    // The session: the last path render, which akr_hip_render_continue extends.  Its
+    // slots are h_tiles / d_pixel, its sampler states d_seed (`seeded`: they hold the state after each
+    // slot's last sample; false after a render of 0 spp, whose slots start from x + y * width) and its
+    // sums d_film.  Every render starts by dropping it (setup_pixels); so do scene, tree and camera changes.
+    struct Session {
+        bool valid = false, seeded = false;
+        uint64_t n = 0;
+        int32_t spp_done = 0, max_depth = 0, flags = 0;
+        float ray_clamp = 0.0f;
+    } session;
+    void drop_session() { session.valid = false; }
+    const Session &require_session() const {
+        if (!session.valid)
+            throw std::runtime_error("no render session to continue (start one with akr_hip_render, akr_hip_render_device "
+                                     "or akr_hip_render_state_import; scene, tree and camera changes and other renders end it)");
+        return session;
+    }
+    void open_session(const akr_pt_params &p, uint64_t N, int32_t spp_done, bool seeded) {
+        session.valid = true;
+        session.seeded = seeded;
+        session.n = N;
+        session.spp_done = spp_done;
+        session.max_depth = p.max_depth;
+        session.flags = p.flags;
+        session.ray_clamp = p.ray_clamp;
+    }
     std::vector<uint32_t> h_pixel;
     bool h_pixel_ok = false;
     DBuf<uint32_t> d_pixel, d_seed, d_slot0, d_slot1, d_counts;
@@ -818,6 +844,7 @@ struct akr_hip_ctx {
         pp.probe_clock = 0;
         pp.order = nullptr;
         pp.fault_test = 0;
+        pp.state_in = pp.state_out = nullptr;
         const uint32_t grid = (uint32_t)std::max<uint64_t>(
             1, std::min<uint64_t>(path_grid[PATH_PLAIN][tab], ((uint64_t)N + kTraceBlock - 1) / kTraceBlock));
         launch_path(true, PATH_PLAIN, tab, pp, grid, ms);
@@ -865,6 +892,7 @@ struct akr_hip_ctx {
         require_ready();
         if (!cam_set) throw std::runtime_error("camera not set (call akr_hip_set_camera)");
         if (n_tiles < 0 || (n_tiles > 0 && !tiles)) throw std::runtime_error("invalid tile list");
+        drop_session();
         h_tiles.clear();
         h_pixel_ok = false;
         uint64_t N = 0;
@@ -887,9 +915,28 @@ struct akr_hip_ctx {
         launch_expand_pixels(d_tiles.p, (uint32_t)h_tiles.size(), (uint32_t)N, d_pixel.p, st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(d_film.p, 0, N * sizeof(float4), st));
+        fork_streams(st);
+        return N;
+    }
+
+    void fork_streams(hipStream_t st) {
         HIPCHK(hipEventRecord(ev_fork, st));  // both internal streams start after the caller's work
         HIPCHK(hipStreamWaitEvent(main_st, ev_fork, 0));
         HIPCHK(hipStreamWaitEvent(side, ev_fork, 0));
+    }
+
+    // setup_pixels for a continued render: the session's pixel list, film and sampler states stay as
+    // they are (nothing is expanded, zeroed or reallocated); only the counters are sized and the
+    // internal streams forked.  Returns the session's pixel count.
+    uint64_t resume_pixels(size_t n_count_words, hipStream_t st) {
+        const uint64_t N = require_session().n;
+        require_ready();
+        if (N != n_pix_last || N > cap) throw std::runtime_error("render session: the slot buffers changed");
+        serialize(st);
+        d_counts.reserve(2 * n_count_words);  // two pass parities
+        if (N == 0) return 0;
+        ensure_side_stream();
+        fork_streams(st);
         return N;
     }
 
@@ -976,7 +1023,9 @@ struct akr_hip_ctx {
         return rg;
     }
 
-    uint64_t render(const akr_pt_params &p, const akr_rect *tiles, int32_t n_tiles, hipStream_t st) {
+    // cont: p.spp more samples for every slot of the session: the slots, their film sums
+    // and (when the session is seeded) their sampler states are the ones the last segment left
+    uint64_t render(const akr_pt_params &p, const akr_rect *tiles, int32_t n_tiles, hipStream_t st, bool cont = false) {
         if (p.spp < 0 || p.max_depth < 0) throw std::runtime_error("spp and max_depth must be >= 0");
         if (p.max_depth > 1000) throw std::runtime_error("max_depth too large");
         // counters per pass, each on its own 128-B line (atomics on one line serialise):
@@ -990,7 +1039,8 @@ struct akr_hip_ctx {
         form_pending = pilot_sum_pending = false;
         probe_ok = false;
         probe_n = 0;
-        const uint64_t N = setup_pixels(tiles, n_tiles, n_count_words, st);
+        const bool resume = cont && require_session().seeded;  // else every slot starts from x + y * width
+        const uint64_t N = cont ? resume_pixels(n_count_words, st) : setup_pixels(tiles, n_tiles, n_count_words, st);
         if (N == 0) return 0;
         if (unchecked_render) {  // a fault raised by an earlier render_device that ran without "verify"
             unchecked_render = false;
@@ -1050,6 +1100,8 @@ struct akr_hip_ctx {
                 pa.fault_test = fault_test ? 1u : 0u;
                 pa.probe_clock = probe_clock ? 1u : 0u;
                 pa.spec_depth = (uint32_t)path_spec_depth;
+                pa.state_in = resume ? d_seed.p : nullptr;  // in place: a slot is fetched by one lane per launch
+                pa.state_out = d_seed.p;
                 // the shading's material / light / CDF tables in LDS when they fit
                 const bool tab = path_tab && path_tab_fits(n_mats, n_lights);
                 // pixels per resident lane of k_path (the occupancy query's grid)
@@ -1073,7 +1125,8 @@ struct akr_hip_ctx {
                 // the pilot can rank pixels for every form (path_order 2), or for k_path only (1)
                 const bool pilot = path_order != 0 && p.spp >= order_min_spp && N >= 2 &&
                                    (path_order == 2 || (!forced || (path_spec != 1 && path_defer == 0)));
-                const bool path_pilot = pilot && path_order_pilot_spp > 0;
+                // a continued render ranks by the camera-ray pilot: the path pilot renders into the film
+                const bool path_pilot = pilot && path_order_pilot_spp > 0 && !cont;
                 // the rule: its size and scene tests, then the camera-ray pilot's mean steps
                 const bool size_ok = ppl1000 <= path_tail_ppl10 * 100;
                 const bool tris_ok = path_defer_min_tris == 0 || (int64_t)n_tris() >= path_defer_min_tris;
@@ -1191,7 +1244,7 @@ struct akr_hip_ctx {
             // L[ps] and the counter set were last used by pass s - 2, whose splat ends its side-stream work
             if (s >= 2) HIPCHK(hipStreamWaitEvent(ms, ev_splat[ps], 0));
             HIPCHK(hipMemsetAsync(cnt, 0, n_count_words * sizeof(uint32_t), ms));
-            RaygenArgs rg = raygen_args((uint32_t)N, L, qcount(0), s == 0);
+            RaygenArgs rg = raygen_args((uint32_t)N, L, qcount(0), s == 0 && !resume);
             rg.probe = probe_p;
             rg.order = worder;
             timed("raygen", ms, [&] { launch_raygen(rg, ms); });
@@ -1552,6 +1605,7 @@ int akr_hip_upload_mesh(akr_hip_ctx *ctx, const float *vertices, uint64_t n_vert
         if (geom_id) *geom_id = (int32_t)ctx->mesh_base.size() - 1;
         ctx->mesh_base.push_back((uint32_t)ctx->n_tris());
         ctx->scene_dirty = true;
+        ctx->drop_session();
         ctx->accel_built = false;
     });
 }
@@ -1573,6 +1627,7 @@ int akr_hip_upload_images(akr_hip_ctx *ctx, const float *rgba, const int32_t *wi
         }
         ctx->images.assign(rgba, rgba + off);
         ctx->scene_dirty = true;
+        ctx->drop_session();
     });
 }
 
@@ -1580,6 +1635,7 @@ int akr_hip_upload_textures(akr_hip_ctx *ctx, const akr_texture *textures, int32
     return guard(ctx, [&] {
         ctx->texs.assign(textures, textures + n);
         ctx->scene_dirty = true;
+        ctx->drop_session();
     });
 }
 
@@ -1587,6 +1643,7 @@ int akr_hip_upload_materials(akr_hip_ctx *ctx, const akr_material *materials, in
     return guard(ctx, [&] {
         ctx->mats.assign(materials, materials + n);
         ctx->scene_dirty = true;
+        ctx->drop_session();
     });
 }
 
@@ -1596,6 +1653,7 @@ int akr_hip_upload_lights(akr_hip_ctx *ctx, const akr_area_light *lights, int32_
         ctx->lights.assign(lights, lights + n);
         ctx->power.assign(power, power + n);
         ctx->scene_dirty = true;
+        ctx->drop_session();
     });
 }
 
@@ -1736,6 +1794,7 @@ int akr_hip_build_accel(akr_hip_ctx *ctx, const akr_build_params *params) {
         p.intersect_cost = 4.0f;
         if (params) p = *params;
         BvhInput in{ctx->verts.data(), ctx->idx.data(), ctx->n_tris()};
+        ctx->drop_session();
         ctx->accel_built = false;  // until the new tree is on the device (a failure below leaves none)
         if (p.builder == AKR_BUILDER_LBVH) build_lbvh_gpu(in, ctx->bvh, ctx->stream);
         else if (p.builder == AKR_BUILDER_SAH || p.builder == AKR_BUILDER_SBVH) build_bvh(in, p, ctx->bvh);
@@ -1756,6 +1815,7 @@ int akr_hip_import_accel(akr_hip_ctx *ctx, const void *nodes, uint64_t n_nodes, 
         int max_leaf = 0;
         const int depth = validate_bvh2(nd, n_nodes, tr, n_tris, ctx->n_tris(), max_leaf);  // throws on bad input
         check_tris_match_mesh(ctx, tr, n_tris, n_threads);  // the records are this scene's triangles
+        ctx->drop_session();
         ctx->accel_built = false;  // until the new tree is on the device (a failure below leaves none)
         BvhOutput &b = ctx->bvh;
         b.nodes.assign(nd, nd + n_nodes);
@@ -1791,6 +1851,7 @@ int akr_hip_set_camera(akr_hip_ctx *ctx, const akr_camera *camera) {
         if (!camera) throw std::runtime_error("null camera");
         ctx->cam = make_camera(*camera);
         ctx->cam_set = true;
+        ctx->drop_session();
     });
 }
 
@@ -2001,7 +2062,9 @@ int akr_hip_render(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_rect
                    float *radiance, float *weight) {
     return guard(ctx, [&] {
         if (!params || !radiance || !weight) throw std::runtime_error("null argument");
-        merge_film(ctx, ctx->render(*params, tiles, n_tiles, ctx->stream), params->spp, radiance, weight);
+        const uint64_t N = ctx->render(*params, tiles, n_tiles, ctx->stream);
+        merge_film(ctx, N, params->spp, radiance, weight);
+        ctx->open_session(*params, N, params->spp, params->spp > 0);
     });
 }
 
@@ -2025,6 +2088,153 @@ int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const a
         ctx->verify_weights(st, N, params->spp);
         ctx->unchecked_render = !ctx->verify;
         ctx->mark_done(st);
+        ctx->open_session(*params, N, params->spp, params->spp > 0);
+    });
+}
+
+namespace {
+constexpr int32_t kMaxSessionSpp = 1 << 24;  // a slot's weight is an f32 count of its samples: exact up to 2^24
+
+// The session's parameters with `spp` more samples, checked
+akr_pt_params continue_params(akr_hip_ctx *ctx, int32_t spp) {
+    const akr_hip_ctx::Session &s = ctx->require_session();
+    if (spp < 0) throw std::runtime_error("spp must be >= 0");
+    if ((int64_t)s.spp_done + spp > kMaxSessionSpp)
+        throw std::runtime_error("render session: " + std::to_string(s.spp_done) + " + " + std::to_string(spp) +
+                                 " samples per slot exceed 2^24 (the weight is an f32 count)");
+    akr_pt_params p{};
+    p.spp = spp;
+    p.max_depth = s.max_depth;
+    p.ray_clamp = s.ray_clamp;
+    p.flags = s.flags;
+    return p;
+}
+}  // namespace
+
+int akr_hip_render_continue(akr_hip_ctx *ctx, int32_t spp, float *radiance, float *weight) {
+    return guard(ctx, [&] {
+        if (!radiance || !weight) throw std::runtime_error("null argument");
+        const akr_pt_params p = continue_params(ctx, spp);
+        akr_hip_ctx::Session s = ctx->session;
+        try {
+            if (spp > 0) {
+                ctx->render(p, nullptr, 0, ctx->stream, true);
+                s.spp_done += spp;
+                s.seeded = true;
+            }
+            merge_film(ctx, s.n, s.spp_done, radiance, weight);
+        } catch (...) {  // a segment that fails leaves no session: its film may be partly extended
+            ctx->drop_session();
+            throw;
+        }
+        ctx->session = s;
+    });
+}
+
+int akr_hip_render_continue_device(akr_hip_ctx *ctx, int32_t spp, float *d_radiance, float *d_weight, void *stream,
+                                   uint64_t *n_pixels) {
+    return guard(ctx, [&] {
+        if (!d_radiance || !d_weight) throw std::runtime_error("null argument");
+        const akr_pt_params p = continue_params(ctx, spp);
+        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        akr_hip_ctx::Session s = ctx->session;
+        const uint64_t N = s.n;
+        try {
+            if (spp > 0) {
+                ctx->render(p, nullptr, 0, st, true);
+                s.spp_done += spp;
+                s.seeded = true;
+            } else {
+                ctx->serialize(st);
+            }
+            if (n_pixels) *n_pixels = N;
+            ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)N, d_radiance, d_weight, st); });
+            HIPCHK(hipGetLastError());
+            ctx->verify_weights(st, N, s.spp_done);
+            if (spp > 0) ctx->unchecked_render = !ctx->verify;
+            ctx->mark_done(st);
+        } catch (...) {
+            ctx->drop_session();
+            throw;
+        }
+        ctx->session = s;
+    });
+}
+
+int akr_hip_render_state_info(akr_hip_ctx *ctx, akr_render_state_info *info) {
+    return guard(ctx, [&] {
+        if (!info) throw std::runtime_error("null argument");
+        const akr_hip_ctx::Session &s = ctx->require_session();
+        *info = akr_render_state_info{};
+        info->n_pixels = s.n;
+        info->spp_done = s.spp_done;
+        info->max_depth = s.max_depth;
+        info->ray_clamp = s.ray_clamp;
+        info->flags = s.flags;
+        info->width = ctx->cam.width;
+        info->height = ctx->cam.height;
+        info->n_tiles = (int32_t)ctx->h_tiles.size();
+    });
+}
+
+int akr_hip_render_state_export(akr_hip_ctx *ctx, uint32_t *sampler, float *film, uint64_t n) {
+    return guard(ctx, [&] {
+        const akr_hip_ctx::Session &s = ctx->require_session();
+        if (n != s.n) throw std::runtime_error("render state export: n is " + std::to_string(n) + ", the session has " +
+                                               std::to_string(s.n) + " slots");
+        if (n == 0) return;
+        if (!sampler || !film) throw std::runtime_error("null argument");
+        hipStream_t st = ctx->stream;
+        ctx->serialize(st);
+        ctx->host_join();
+        if (s.seeded) {
+            HIPCHK(hipMemcpyAsync(sampler, ctx->d_seed.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        } else {  // no sample drawn yet: the slots' start states
+            const int W = ctx->cam.width;
+            const std::vector<uint32_t> &pl = ctx->host_pixels();
+            for (uint64_t k = 0; k < n; k++) sampler[k] = (uint32_t)((int)(pl[k] & 0xFFFFu) + (int)(pl[k] >> 16) * W);
+        }
+        HIPCHK(hipMemcpyAsync(film, ctx->d_film.p, n * sizeof(float4), hipMemcpyDeviceToHost, st));
+        ctx->mark_done(st);
+        HIPCHK(hipStreamSynchronize(st));
+    });
+}
+
+int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_rect *tiles, int32_t n_tiles,
+                                const uint32_t *sampler, const float *film, uint64_t n) {
+    return guard(ctx, [&] {
+        if (!params) throw std::runtime_error("null argument");
+        if (params->spp < 0 || params->max_depth < 0) throw std::runtime_error("spp and max_depth must be >= 0");
+        if (params->max_depth > 1000) throw std::runtime_error("max_depth too large");
+        if (params->spp > kMaxSessionSpp) throw std::runtime_error("render state import: spp exceeds 2^24");
+        if (n && (!sampler || !film)) throw std::runtime_error("null argument");
+        if (!ctx->cam_set) throw std::runtime_error("camera not set (call akr_hip_set_camera)");
+        if (n_tiles < 0 || (n_tiles > 0 && !tiles)) throw std::runtime_error("invalid tile list");
+        // validated before anything of the context changes: a refused import keeps the current session
+        uint64_t want = 0;
+        for (int k = 0; k < n_tiles; k++) {
+            const int x0 = std::max(0, tiles[k].x0), y0 = std::max(0, tiles[k].y0);
+            const int x1 = std::min(ctx->cam.width, tiles[k].x1), y1 = std::min(ctx->cam.height, tiles[k].y1);
+            if (x1 > x0 && y1 > y0) want += (uint64_t)(x1 - x0) * (uint64_t)(y1 - y0);
+        }
+        if (n != want) throw std::runtime_error("render state import: n is " + std::to_string(n) + ", the tile list has " +
+                                                std::to_string(want) + " pixels");
+        for (uint64_t k = 0; k < n; k++)
+            if (film[4 * k + 3] != (float)params->spp)
+                throw std::runtime_error("render state import: slot " + std::to_string(k) + " holds weight " +
+                                         std::to_string(film[4 * k + 3]) + ", not spp " + std::to_string(params->spp));
+        hipStream_t st = ctx->stream;
+        const uint64_t N = ctx->setup_pixels(tiles, n_tiles, 0, st);  // the slots, as a render lays them out
+        if (N != n) throw std::runtime_error("render state import: slot count changed");
+        if (N) {
+            HIPCHK(hipMemcpyAsync(ctx->d_seed.p, sampler, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->d_film.p, film, N * sizeof(float4), hipMemcpyHostToDevice, st));
+        }
+        ctx->mark_done(st);
+        HIPCHK(hipStreamSynchronize(st));  // the caller's arrays are free again
+        ctx->probe_ok = false;
+        ctx->probe_n = 0;
+        ctx->open_session(*params, N, params->spp, true);
     });
 }
 

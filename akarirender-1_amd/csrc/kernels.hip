@@ -1798,6 +1798,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 splat_one(film, make_float4(Lr.x, Lr.y, Lr.z, 0.0f), pa.ray_clamp);
                 if (--left == 0) {
                     pa.film[pix] = film;
+                    if (pa.state_out) pa.state_out[pix] = seed;  // where a continued render resumes
                     if (pa.probe)
                         pa.probe[pix] = make_uint4(seed, COUNT ? pc_closest : 0u, COUNT ? pc_shadow : 0u,
                                                    probe_flags<COUNT>(pa));
@@ -1813,8 +1814,13 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 const uint32_t px = pa.pixel[pix];
                 pxr = px;
                 left = pa.spp;
-                seed = (uint32_t)((int)(px & 0xFFFFu) + (int)(px >> 16) * pa.cam.width);
-                film = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (pa.state_in) {  // a continued render (wave-uniform): the state and sums the last segment left
+                    seed = pa.state_in[pix];
+                    film = pa.film[pix];
+                } else {
+                    seed = (uint32_t)((int)(px & 0xFFFFu) + (int)(px >> 16) * pa.cam.width);
+                    film = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                }
                 start = true;
                 if (COUNT) pc_closest = pc_shadow = 0;
             }
@@ -2130,6 +2136,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
             // 4. a finished pixel stores its film and fetches the next; free lanes start samples
             const bool free_lane = !busy && !fresh && !want_sh && s.kind() == RAY_NONE;
             if (free_lane && !done && !need_pixel && !s.running() && left == 0 && s.open() == 0) {
+                if (pa.state_out) pa.state_out[pix] = seed;
                 if (pa.probe)
                     pa.probe[pix] = make_uint4(seed, COUNT ? pc_closest : 0u, COUNT ? pc_shadow : 0u,
                                                probe_flags<COUNT>(pa));
@@ -2141,7 +2148,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
             if (asked && !need_pixel) {
                 pxy = pa.pixel[pix];
                 left = pa.spp;
-                seed = (uint32_t)((int)(pxy & 0xFFFFu) + (int)(pxy >> 16) * pa.cam.width);
+                // a continued render (wave-uniform) resumes the slot's sampler; its film sums are in its film slot
+                seed = pa.state_in ? pa.state_in[pix]
+                                   : (uint32_t)((int)(pxy & 0xFFFFu) + (int)(pxy >> 16) * pa.cam.width);
                 if (COUNT) pc_closest = pc_shadow = 0;
             }
             try_start(free_lane, fresh, ra, rb);
@@ -2440,6 +2449,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                     occ = 0;
                     s.set(SpecState::SEND, 1, 0);
                     if (cseq == spp) {
+                        if (pa.state_out) pa.state_out[pix] = C;
                         if (pa.probe)
                             pa.probe[pix] = make_uint4(C, COUNT ? pc_closest : 0u, COUNT ? pc_shadow : 0u, probe_flags<COUNT>(pa));
                         s.set(SpecState::ROLE, 2, ROLE_FREE);
@@ -2454,7 +2464,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 fetch_pixels(f, n, pa.work, pa.order ? pa.order_mode : FETCH_LINEAR, pa.order, pa.prio, need, done, pix);
                 if (asked && !need) {
                     const uint32_t px = pa.pixel[pix];
-                    C = (uint32_t)((int)(px & 0xFFFFu) + (int)(px >> 16) * pa.cam.width);
+                    // a continued render (wave-uniform) resumes from the committed state the last segment left
+                    C = pa.state_in ? pa.state_in[pix] : (uint32_t)((int)(px & 0xFFFFu) + (int)(px >> 16) * pa.cam.width);
                     cseq = 0;
                     occ = 0;
                     grp = 1ull << lane;
@@ -2534,6 +2545,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
             // a pixel that is done frees its group
             {
                 if (s.role() == ROLE_OWNER && cseq == spp) {
+                    if (pa.state_out) pa.state_out[pix] = C;
                     if (pa.probe)
                         pa.probe[pix] = make_uint4(C, COUNT ? pc_closest : 0u, COUNT ? pc_shadow : 0u, probe_flags<COUNT>(pa));
                     s.set(SpecState::ROLE, 2, ROLE_FREE);
@@ -2562,7 +2574,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 fetch_pixels(f, n, pa.work, pa.order ? pa.order_mode : FETCH_LINEAR, pa.order, pa.prio, need, done, pix);
                 if (asked && !need) {
                     const uint32_t px = pa.pixel[pix];
-                    C = (uint32_t)((int)(px & 0xFFFFu) + (int)(px >> 16) * pa.cam.width);
+                    // a continued render (wave-uniform) resumes from the committed state the last segment left
+                    C = pa.state_in ? pa.state_in[pix] : (uint32_t)((int)(px & 0xFFFFu) + (int)(px >> 16) * pa.cam.width);
                     cseq = 0;
                     occ = 0;
                     grp = 1ull << lane;

@@ -47,7 +47,8 @@ extern "C" {
 #endif
 
 /* 2: akr_trace_counts gained deep_rays[3]; akr_pixel_probe / akr_hip_pixel_probe added
- * 3: akr_trace_counts gained leaf_tests[3] */
+ * 3: akr_trace_counts gained leaf_tests[3]
+ *    (still 3 with the render session calls below: they only add exports and change no struct layout) */
 #define AKR_HIP_API_VERSION 3
 
 typedef struct akr_hip_ctx akr_hip_ctx;
@@ -286,6 +287,56 @@ int akr_hip_render_node(akr_hip_ctx *const *ctxs, int32_t n_ctx, const akr_pt_pa
 int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_rect *tiles,
                           int32_t n_tiles, float *d_radiance, float *d_weight, void *stream,
                           uint64_t *n_pixels);
+
+/* ---- Render sessions: continue a finished path render.
+ *
+ * A context remembers its last path render as a session: the tile list and its packed film slots,
+ * max_depth, ray_clamp, flags, the camera resolution, and per slot the samples done, the film sums
+ * and the LCG sampler state after the last sample.  A continue renders `spp` more samples per slot
+ * from exactly there, so a render of a spp continued by b spp equals one render of a + b spp bit for
+ * bit, in radiance, weight and sampler state, whichever form ran each segment.
+ *
+ *  - akr_hip_render and akr_hip_render_device start a new session (replacing any earlier one), and so
+ *    does akr_hip_render_state_import.  A continue extends the session.
+ *  - akr_hip_upload_mesh / _images / _textures / _materials / _lights, akr_hip_build_accel,
+ *    akr_hip_import_accel, akr_hip_set_camera, akr_hip_render_ao, and akr_hip_render_node on a member
+ *    context end it.  A continue without a session returns a non-zero status whose message begins
+ *    "no render session to continue"; the context stays usable.  A continue that fails while
+ *    rendering ends the session (its film may be partly extended).
+ *  - akr_hip_trace, akr_hip_trace_device and the query calls keep it.
+ *  - akr_hip_set_option between segments is allowed, and may switch the render form, the cost order
+ *    and exact_cull: all give the same bits.
+ *  - spp = 0 renders nothing and returns the totals.  A total above 2^24 samples per slot is refused
+ *    (the weight is an f32 count); the session stays.
+ *  - The film checks (option "verify") compare every slot's weight with the session's total.
+ *  - With option "pixel_probe" the probe of a continue holds each slot's sampler state after the
+ *    total, and the ray counts of that segment alone. */
+typedef struct akr_render_state_info {
+    uint64_t n_pixels;            /* film slots, packed tile order */
+    int32_t spp_done, max_depth;
+    float ray_clamp;
+    int32_t flags;
+    int32_t width, height, n_tiles, _pad;  /* n_tiles: the clipped, non-empty tiles */
+} akr_render_state_info;
+
+/* spp more samples per slot of the context's session.  Host form: ADDS the session's totals to
+ * full-frame buffers exactly as akr_hip_render of spp_done + spp samples would have (pass zeroed
+ * buffers to get the film).  Synchronous. */
+int akr_hip_render_continue(akr_hip_ctx *ctx, int32_t spp, float *radiance, float *weight);
+/* Device form: overwrites packed buffers with the session's totals like akr_hip_render_device, with
+ * the same "verify" behaviour. */
+int akr_hip_render_continue_device(akr_hip_ctx *ctx, int32_t spp, float *d_radiance, float *d_weight,
+                                   void *stream, uint64_t *n_pixels);
+int akr_hip_render_state_info(akr_hip_ctx *ctx, akr_render_state_info *info);
+/* The session's state to host memory, n = its n_pixels: sampler[n] (LCG state after each slot's
+ * last sample; x + y * width where no sample was drawn), film[n][4] (sum r, g, b, weight). */
+int akr_hip_render_state_export(akr_hip_ctx *ctx, uint32_t *sampler, float *film, uint64_t n);
+/* Establish a session as if params->spp samples had just been rendered over `tiles` (the context
+ * holds the scene, tree and camera): n must equal the clipped tile list's pixel count and every
+ * film[k][3] must equal params->spp, else the call is refused and changes nothing.  Seeds
+ * x + y * width, a zero film and spp 0, continued, reproduce a fresh render. */
+int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_rect *tiles,
+                                int32_t n_tiles, const uint32_t *sampler, const float *film, uint64_t n);
 
 /* Host-only BVH build (no device needed): the same builder akr_hip_build_accel runs, for tools
  * and CPU-side checks.  Arrays are owned by the handle; free with akr_bvh_host_free. */
