@@ -107,6 +107,16 @@ class RenderStateInfo(C.Structure):
                 ("n_tiles", C.c_int32), ("_pad", C.c_int32)]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_spp", C.c_int32), ("pass_spp", C.c_int32), ("threshold", C.c_float), ("_pad", C.c_int32)]
+
+
+class AdaptiveInfo(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("spp_min", C.c_int32), ("spp_max", C.c_int32), ("_pad", C.c_int32),
+                ("samples", C.c_uint64), ("strips", C.c_uint64), ("strips_at_cap", C.c_uint64)]
+
+
+STRIP = 64   # slots per strip of the adaptive convergence test (packed tile order)
 MAX_SESSION_SPP = 1 << 24   # a slot's weight is an f32 count of its samples
 TEX_CONSTANT, TEX_IMAGE = 0, 1
 PT_EXACT_CULL = 1
@@ -184,6 +194,18 @@ EXPORTS = {
     "akr_hip_render_state_info": (C.c_int, [_P, C.POINTER(RenderStateInfo)]),
     "akr_hip_render_state_export": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "akr_hip_render_state_import": (C.c_int, [_P, C.POINTER(PtParams), _P, C.c_int32, _P, _P, C.c_uint64]),
+    "akr_hip_render_continue_masked": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, _P, _P]),
+    "akr_hip_render_continue_masked_device": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, _P, _P, _P,
+                                                        C.POINTER(C.c_uint64)]),
+    "akr_hip_render_state_spp_range": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "akr_hip_render_adaptive": (C.c_int, [_P, C.POINTER(PtParams), C.POINTER(AdaptiveParams), _P, C.c_int32, _P, _P,
+                                          C.POINTER(AdaptiveInfo)]),
+    "akr_hip_render_adaptive_device": (C.c_int, [_P, C.POINTER(PtParams), C.POINTER(AdaptiveParams), _P, C.c_int32,
+                                                 _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(AdaptiveInfo)]),
+    "akr_hip_adaptive_begin": (C.c_int, [_P, C.POINTER(PtParams), C.POINTER(AdaptiveParams), _P, C.c_int32,
+                                         C.POINTER(AdaptiveInfo), C.POINTER(C.c_int32)]),
+    "akr_hip_adaptive_step": (C.c_int, [_P, C.POINTER(AdaptiveInfo), C.POINTER(C.c_int32)]),
+    "akr_hip_adaptive_error": (C.c_int, [_P, _P, _P, C.c_uint64]),
 }
 
 _lib = None
@@ -509,6 +531,102 @@ class HipContext:
         arr, n = self._rects(tiles)
         self._check(self.lib.akr_hip_render_state_import(self.h, C.byref(p), _arr_ptr(arr), n, _ptr(sampler),
                                                          _ptr(film), sampler.size))
+
+    # ---- sessions whose slots hold different counts, adaptive sampling
+
+    def render_continue_masked(self, spp, mask, width, height, radiance=None, weight=None):
+        """`spp` more samples for the slots whose byte of `mask` (uint8[n_pixels], packed tile order) is
+        non-zero; the session's totals are added to the full-frame host buffers like render_continue."""
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if radiance is None:
+            radiance = np.zeros((height, width, 3), np.float32)
+        if weight is None:
+            weight = np.zeros((height, width), np.float32)
+        assert radiance.dtype == np.float32 and radiance.flags.c_contiguous and radiance.size == 3 * width * height
+        assert weight.dtype == np.float32 and weight.flags.c_contiguous and weight.size == width * height
+        self._check(self.lib.akr_hip_render_continue_masked(self.h, int(spp), _ptr(mask), mask.size, _ptr(radiance),
+                                                            _ptr(weight)))
+        return radiance, weight
+
+    def render_continue_masked_device(self, spp, d_mask: int, n: int, d_radiance: int, d_weight: int, stream: int = 0):
+        """Device form: `d_mask` is a device pointer to uint8[n]; packed device buffers are overwritten."""
+        npx = C.c_uint64(0)
+        self._check(self.lib.akr_hip_render_continue_masked_device(
+            self.h, int(spp), C.c_void_p(d_mask), int(n), C.c_void_p(d_radiance), C.c_void_p(d_weight),
+            C.c_void_p(stream), C.byref(npx)))
+        return npx.value
+
+    def render_state_spp_range(self):
+        """(smallest, largest) sample count of the session's slots."""
+        lo, hi = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.akr_hip_render_state_spp_range(self.h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    @staticmethod
+    def _adaptive_params(min_spp, pass_spp, threshold):
+        return AdaptiveParams(int(min_spp), int(pass_spp), float(threshold), 0)
+
+    @staticmethod
+    def _adaptive_info(info):
+        return {k: getattr(info, k) for k, _ in AdaptiveInfo._fields_ if k != "_pad"}
+
+    def render_adaptive(self, cap_spp, max_depth, tiles, width, height, threshold, min_spp=16, pass_spp=0,
+                        ray_clamp=0.0, radiance=None, weight=None, exact_cull=False):
+        """Adaptive render (akr_hip_render_adaptive): min_spp for every slot, then passes over the strips
+        whose error is above `threshold`, up to cap_spp.  Returns (radiance, weight, info dict)."""
+        if radiance is None:
+            radiance = np.zeros((height, width, 3), np.float32)
+        if weight is None:
+            weight = np.zeros((height, width), np.float32)
+        assert radiance.dtype == np.float32 and radiance.flags.c_contiguous and radiance.size == 3 * width * height
+        assert weight.dtype == np.float32 and weight.flags.c_contiguous and weight.size == width * height
+        p = PtParams(int(cap_spp), int(max_depth), float(ray_clamp), PT_EXACT_CULL if exact_cull else 0)
+        ap = self._adaptive_params(min_spp, pass_spp, threshold)
+        info = AdaptiveInfo()
+        arr, n = self._rects(tiles)
+        self._check(self.lib.akr_hip_render_adaptive(self.h, C.byref(p), C.byref(ap), _arr_ptr(arr), n, _ptr(radiance),
+                                                     _ptr(weight), C.byref(info)))
+        return radiance, weight, self._adaptive_info(info)
+
+    def render_adaptive_device(self, cap_spp, max_depth, tiles, d_radiance: int, d_weight: int, threshold, min_spp=16,
+                               pass_spp=0, stream: int = 0, ray_clamp=0.0):
+        """Device form: packed device buffers are overwritten; returns (slot count, info dict)."""
+        p = PtParams(int(cap_spp), int(max_depth), float(ray_clamp), 0)
+        ap = self._adaptive_params(min_spp, pass_spp, threshold)
+        info = AdaptiveInfo()
+        arr, n = self._rects(tiles)
+        npx = C.c_uint64(0)
+        self._check(self.lib.akr_hip_render_adaptive_device(
+            self.h, C.byref(p), C.byref(ap), _arr_ptr(arr), n, C.c_void_p(d_radiance), C.c_void_p(d_weight),
+            C.c_void_p(stream), C.byref(npx), C.byref(info)))
+        return npx.value, self._adaptive_info(info)
+
+    def adaptive_begin(self, cap_spp, max_depth, tiles, threshold, min_spp=16, pass_spp=0, ray_clamp=0.0,
+                       exact_cull=False):
+        """The adaptive render one pass at a time: min_spp for every slot and the snapshot.  Returns
+        (info dict, more); while `more`, adaptive_step() runs the next pass and its test, and
+        render_continue(0, ...) returns the film so far."""
+        p = PtParams(int(cap_spp), int(max_depth), float(ray_clamp), PT_EXACT_CULL if exact_cull else 0)
+        ap = self._adaptive_params(min_spp, pass_spp, threshold)
+        info, more = AdaptiveInfo(), C.c_int32(0)
+        arr, n = self._rects(tiles)
+        self._check(self.lib.akr_hip_adaptive_begin(self.h, C.byref(p), C.byref(ap), _arr_ptr(arr), n, C.byref(info),
+                                                    C.byref(more)))
+        return self._adaptive_info(info), bool(more.value)
+
+    def adaptive_step(self):
+        info, more = AdaptiveInfo(), C.c_int32(0)
+        self._check(self.lib.akr_hip_adaptive_step(self.h, C.byref(info), C.byref(more)))
+        return self._adaptive_info(info), bool(more.value)
+
+    def adaptive_error(self):
+        """The last convergence test of the session's adaptive render: (strip_error float32[n_strips],
+        strip_active uint8[n_strips]), one strip per 64 slots in packed tile order."""
+        n = (self.render_state_info()["n_pixels"] + STRIP - 1) // STRIP
+        err = np.zeros(n, np.float32)
+        act = np.zeros(n, np.uint8)
+        self._check(self.lib.akr_hip_adaptive_error(self.h, _ptr(err), _ptr(act), n))
+        return err, act
 
     def ray_steps(self, n: int) -> np.ndarray:
         """Per-ray traversal iterations of the last standalone trace (option "ray_steps")."""

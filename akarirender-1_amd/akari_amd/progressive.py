@@ -88,6 +88,63 @@ def render_progressive(ctx: "capi.HipContext", spp: int, max_depth: int, tiles, 
     return rad, wt, done
 
 
+def adaptive_totals(min_spp: int, pass_spp: int, cap: int) -> List[int]:
+    """The sample counts a still-active slot of an adaptive render passes through:
+    min_spp, then pass_spp more per pass (0: each pass doubles the count), clipped at `cap`.  A cap at
+    or below min_spp is a plain render of `cap` samples: one total, no test."""
+    min_spp, pass_spp, cap = int(min_spp), int(pass_spp), int(cap)
+    if min_spp < 1:
+        raise ValueError("min_spp must be at least 1")
+    if pass_spp < 0:
+        raise ValueError("pass_spp must be >= 0 (0: passes double)")
+    if cap < 0:
+        raise ValueError("the cap must be >= 0")
+    out = [min(min_spp, cap)]
+    while out[-1] < cap:
+        out.append(min(cap, out[-1] + pass_spp if pass_spp > 0 else 2 * out[-1]))
+    return out
+
+
+def check_adaptive_args(threshold: float, min_spp: int, pass_spp: int, cap: int) -> None:
+    """The argument rules of an adaptive render, checked before a device is touched."""
+    t = float(threshold)
+    if not t >= 0.0:  # NaN fails too
+        raise ValueError("the adaptive threshold must be >= 0 and not NaN")
+    adaptive_totals(min_spp, pass_spp, cap)
+    if int(cap) > capi.MAX_SESSION_SPP:
+        raise ValueError("the cap exceeds 2^24 samples per pixel")
+
+
+def render_adaptive(ctx: "capi.HipContext", cap_spp: int, max_depth: int, tiles, width: int, height: int,
+                    threshold: float, min_spp: int = 16, pass_spp: int = 0, on_pass: Optional[Callable] = None,
+                    time_budget: Optional[float] = None, ray_clamp: float = 0.0, exact_cull: bool = False,
+                    clock: Callable[[], float] = time.monotonic):
+    """Adaptive render of `tiles`: returns (radiance, weight, info).
+
+    Every pixel gets min_spp samples; then passes add samples to the 64-slot strips whose error is above
+    `threshold` (pass_spp per pass, 0: doubling), up to cap_spp.  The weight holds each pixel's sample
+    count; info has passes, spp_min, spp_max, samples, strips and strips_at_cap.  Without on_pass and
+    time_budget this is one library call; with either, the render runs pass by pass: after each pass
+    `on_pass(info, radiance, weight)` gets the film so far (a true return stops the render), and
+    `time_budget` (seconds) stops it after the first pass that ends past the budget.  The passes done
+    give the same film either way."""
+    check_adaptive_args(threshold, min_spp, pass_spp, cap_spp)
+    if on_pass is None and time_budget is None:
+        return ctx.render_adaptive(cap_spp, max_depth, tiles, width, height, threshold, min_spp=min_spp,
+                                   pass_spp=pass_spp, ray_clamp=ray_clamp, exact_cull=exact_cull)
+    t0 = clock()
+    info, more = ctx.adaptive_begin(cap_spp, max_depth, tiles, threshold, min_spp=min_spp, pass_spp=pass_spp,
+                                    ray_clamp=ray_clamp, exact_cull=exact_cull)
+    while True:
+        rad, wt = ctx.render_continue(0, width, height)
+        if on_pass is not None and on_pass(info, rad, wt):
+            break
+        if not more or (time_budget is not None and clock() - t0 >= time_budget):
+            break
+        info, more = ctx.adaptive_step()
+    return rad, wt, info
+
+
 def scene_fingerprint(cs) -> str:
     """SHA-256 over a CompiledScene's arrays and camera: what a film's samples depend on."""
     h = hashlib.sha256()

@@ -14,6 +14,10 @@ Usage: python -m akari_amd.render scene.akari [--out image.png|.pfm] [--gpus N]
 The second line renders a Path scene on one GPU in passes (akari_amd/progressive.py): the output is
 rewritten after each pass, the render stops after the pass that exceeds the budget, the session is
 saved after each pass, or a saved one is continued up to the scene's spp.
+       ... --adaptive THRESHOLD [--min-spp N] [--pass-spp N] [--spp-map FILE.pfm] [--preview] [--time-budget S]
+The third line renders a Path scene adaptively: N samples for every pixel (default
+16), then passes only over the 64-pixel strips whose error is above THRESHOLD, up to the scene's spp
+(the cap); --spp-map writes each pixel's sample count.  Checkpoints do not hold an adaptive film.
 """
 from __future__ import annotations
 
@@ -98,6 +102,30 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
                                               resume=ck is not None)
 
 
+def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, min_spp: int = 16,
+                          pass_spp: Optional[int] = None, on_pass=None, time_budget: Optional[float] = None,
+                          **build_kw):
+    """Render a Path scene adaptively on one device; returns (radiance, weight, info).  The integrator's
+    spp is the cap; weight holds each pixel's sample count (progressive.render_adaptive)."""
+    it = sc.integrator
+    if not isinstance(it, scene.PathIntegrator):
+        raise ValueError("adaptive rendering needs the Path integrator")
+    progressive.check_adaptive_args(threshold, min_spp, pass_spp or 0, it.spp)
+    cs = scene.compile_scene(sc)
+    w, h = (int(v) for v in sc.camera.resolution)
+    with capi.HipContext(device) as ctx:
+        scene.upload_scene(ctx, cs, **build_kw)
+        return progressive.render_adaptive(ctx, it.spp, it.max_depth, _tiles(sc, it.tile_size), w, h, threshold,
+                                           min_spp=min_spp, pass_spp=pass_spp or 0, on_pass=on_pass,
+                                           time_budget=time_budget, ray_clamp=it.ray_clamp)
+
+
+def write_spp_map(path: str, weight: np.ndarray) -> None:
+    """Each pixel's sample count as a linear float map (the count in all three channels)."""
+    counts = np.repeat(np.asarray(weight, np.float32)[..., None], 3, axis=-1)
+    film.write_pfm(path, counts, np.ones_like(weight, dtype=np.float32))
+
+
 def write_film(path: str, radiance: np.ndarray, weight: np.ndarray) -> None:
     """Film::write_image (core/film.h:97-113): PNG is sRGB 8-bit, PFM keeps linear floats."""
     if path.lower().endswith(".pfm"):
@@ -119,8 +147,25 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     help="stop after the first pass that ends past this many seconds of rendering")
     ap.add_argument("--checkpoint", default=None, metavar="FILE", help="save the render session after each pass")
     ap.add_argument("--resume", default=None, metavar="FILE", help="continue a saved session up to the scene's spp")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
+                    help="adaptive sampling: stop sampling a 64-pixel strip once its error is at or below THRESHOLD; "
+                         "the scene's spp (or --spp) is the cap")
+    ap.add_argument("--min-spp", type=int, default=16, metavar="N",
+                    help="with --adaptive: samples every pixel gets before the first test (default 16)")
+    ap.add_argument("--spp-map", default=None, metavar="FILE.pfm",
+                    help="with --adaptive: write each pixel's sample count")
     args = ap.parse_args(argv)
-    passes = (args.pass_spp is not None or args.preview or args.time_budget is not None or
+    if args.adaptive is not None:  # refused before the scene is read
+        if args.checkpoint is not None or args.resume is not None:
+            ap.error("--adaptive cannot be combined with --checkpoint or --resume: a checkpoint holds a film "
+                     "with one sample count for every pixel")
+        if not args.adaptive >= 0:
+            ap.error("--adaptive needs a threshold >= 0")
+        if args.min_spp < 1:
+            ap.error("--min-spp needs at least one sample")
+    elif args.spp_map is not None:
+        ap.error("--spp-map needs --adaptive")
+    passes = args.adaptive is not None or (args.pass_spp is not None or args.preview or args.time_budget is not None or
               args.checkpoint is not None or args.resume is not None)
     if passes:  # checked before the scene is uploaded: no device is needed to refuse these
         if args.gpus != 1:
@@ -135,11 +180,28 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if args.spp is not None:
         sc.integrator.spp = args.spp
     if passes and not isinstance(sc.integrator, scene.PathIntegrator):
-        ap.error(f"--pass-spp, --preview, --time-budget, --checkpoint and --resume need the Path integrator; "
+        ap.error(f"--pass-spp, --preview, --time-budget, --checkpoint, --resume and --adaptive need the Path integrator; "
                  f"the scene's is {type(sc.integrator).__name__}")
     out = args.out or sc.output
     t0 = time.time()
-    if passes:
+    if args.adaptive is not None:
+        def show_adaptive(info, rad, wt):
+            if args.preview:
+                write_film(out, rad, wt)
+                print(f"pass {info['passes']} to {info['spp_max']} spp, {info['samples']} samples: "
+                      f"{time.time() - t0:.2f}s -> {out}", flush=True)
+
+        try:
+            per_pass = args.preview or args.time_budget is not None
+            rad, wt, info = render_scene_adaptive(sc, args.adaptive, 0, min_spp=args.min_spp, pass_spp=args.pass_spp,
+                                                  on_pass=show_adaptive if per_pass else None,
+                                                  time_budget=args.time_budget)
+        except ValueError as e:
+            ap.error(str(e))
+        done = f"{info['spp_min']}..{info['spp_max']} ({info['samples']} samples in {info['passes']} passes)"
+        if args.spp_map is not None:
+            write_spp_map(args.spp_map, wt)
+    elif passes:
         def show(done, rad, wt):
             if args.preview:
                 write_film(out, rad, wt)

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <string>
 #include <limits>
+#include <utility>
 #include <vector>
 
 #include "../../include/akr_hip.h"
@@ -279,6 +280,49 @@ class HipPathTracer {
               akr_hip_render_state_import(scene.handle(), &p, tiles.data(), (int32_t)tiles.size(), sampler.data(),
                                           sums.data(), sampler.size()),
               "render_state_import");
+    }
+
+    // Adaptive sampling (include/akr_hip.h).  render_continue_masked: `more` samples for
+    // the slots whose byte of `mask` (packed tile order, one per slot of the session) is non-zero; the
+    // film is cleared and then holds the session's totals.
+    void render_continue_masked(const HipAccelerator &scene, int more, const std::vector<uint8_t> &mask, Film &film) const {
+        std::fill(film.radiance.begin(), film.radiance.end(), 0.0f);
+        std::fill(film.weight.begin(), film.weight.end(), 0.0f);
+        check(scene.handle(),
+              akr_hip_render_continue_masked(scene.handle(), more, mask.data(), mask.size(), film.radiance.data(),
+                                             film.weight.data()),
+              "render_continue_masked");
+    }
+    // this tracer's spp is the cap: min_spp for every pixel, then passes over the 64-slot strips whose
+    // error is above `threshold` (pass_spp 0: each pass doubles their count); accumulates into the film
+    akr_adaptive_info render_adaptive(const HipAccelerator &scene, Film &film, float threshold, int min_spp = 16,
+                                      int pass_spp = 0) const {
+        std::vector<akr_rect> tiles;
+        for (int y = 0; y < film.height; y += tile_size)
+            for (int x = 0; x < film.width; x += tile_size) tiles.push_back({x, y, x + tile_size, y + tile_size});
+        akr_pt_params p{spp, max_depth, ray_clamp, 0};
+        akr_adaptive_params ap{min_spp, pass_spp, threshold, 0};
+        akr_adaptive_info info;
+        check(scene.handle(),
+              akr_hip_render_adaptive(scene.handle(), &p, &ap, tiles.data(), (int32_t)tiles.size(), film.radiance.data(),
+                                      film.weight.data(), &info),
+              "render_adaptive");
+        return info;
+    }
+    // the last convergence test: each strip's error and whether it is still active
+    void adaptive_error(const HipAccelerator &scene, std::vector<float> &strip_error,
+                        std::vector<uint8_t> &strip_active) const {
+        const uint64_t n = (render_state_info(scene).n_pixels + 63) / 64;
+        strip_error.resize(n);
+        strip_active.resize(n);
+        check(scene.handle(), akr_hip_adaptive_error(scene.handle(), strip_error.data(), strip_active.data(), n),
+              "adaptive_error");
+    }
+    // the smallest and the largest sample count of the session's slots
+    std::pair<int, int> render_state_spp_range(const HipAccelerator &scene) const {
+        int32_t lo = 0, hi = 0;
+        check(scene.handle(), akr_hip_render_state_spp_range(scene.handle(), &lo, &hi), "render_state_spp_range");
+        return {lo, hi};
     }
 
     // Multi-GPU in one process (akr_hip_render_node): tile j on accelerators[j % n], one per device,

@@ -231,6 +231,21 @@ struct akr_hip_ctx {
         uint64_t n = 0;
         int32_t spp_done = 0, max_depth = 0, flags = 0;
         float ray_clamp = 0.0f;
+        // Slots that hold different sample counts (masked continues): spp_done is then the
+        // largest count, spp_min the smallest, and d_count holds every slot's expected count
+        bool uniform = true;
+        int32_t spp_min = 0;
+        // the last adaptive render's strips, for akr_hip_adaptive_error (0: none)
+        uint64_t n_strips = 0;
+        // an adaptive render in progress (akr_hip_adaptive_begin / _step): every active strip holds
+        // `total` samples, `m` slots are active; a continue that draws samples ends it (on = false)
+        struct Adaptive {
+            bool on = false, more = false, some_stopped = false;
+            int32_t cap = 0, pass_spp = 0, total = 0;
+            float threshold = 0.0f;
+            uint32_t m = 0;
+            akr_adaptive_info info{};
+        } ad;
     } session;
     void drop_session() { session.valid = false; }
     const Session &require_session() const {
@@ -247,7 +262,18 @@ struct akr_hip_ctx {
         session.max_depth = p.max_depth;
         session.flags = p.flags;
         session.ray_clamp = p.ray_clamp;
+        session.uniform = true;
+        session.spp_min = spp_done;
+        session.n_strips = 0;
+        session.ad = Session::Adaptive{};
     }
+    // Adaptive sampling: the active-slot list of a subset pass and its compaction
+    // scratch, the per-slot expected counts of a non-uniform session, and the convergence test's
+    // snapshot, slot mask and per-strip results
+    DBuf<uint32_t> d_count, d_active, d_wcount, d_woff, d_nactive, d_crange;
+    DBuf<uint8_t> d_mask, d_scan_tmp, d_strip_active;
+    DBuf<float> d_strip_err;
+    DBuf<float4> d_prev;
     std::vector<uint32_t> h_pixel;
     bool h_pixel_ok = false;
     DBuf<uint32_t> d_pixel, d_seed, d_slot0, d_slot1, d_counts;
@@ -969,8 +995,10 @@ struct akr_hip_ctx {
     // In-band check (option "verify"): every one of the N film slots holds exactly `spp` samples.
     // Runs on `st` after the render has been joined into it and waits for it on the host, so a
     // render_device with the check on returns only after the film is complete.
-    void verify_weights(hipStream_t st, uint64_t N, int spp) {
+    // per_slot: the film of a session whose slots hold different counts: every weight against d_count
+    void verify_weights(hipStream_t st, uint64_t N, int spp, bool per_slot = false) {
         if (!verify || N == 0) return;
+        if (per_slot && d_count.n < N) throw std::runtime_error("film check: the per-slot counts are missing");
         if (!h_check) {
             HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_check), sizeof(uint32_t),
                                  hipHostMallocMapped | hipHostMallocCoherent));
@@ -979,7 +1007,8 @@ struct akr_hip_ctx {
         d_bad.reserve(1);
         *reinterpret_cast<volatile uint32_t *>(h_check) = kMappedSentinel;
         HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), st));
-        launch_check_weights(d_film.p, (uint32_t)N, (float)spp, d_bad.p, st);
+        if (per_slot) launch_check_counts(d_film.p, d_count.p, (uint32_t)N, d_bad.p, st);
+        else launch_check_weights(d_film.p, (uint32_t)N, (float)spp, d_bad.p, st);
         launch_store_word(d_bad.p, d_check_host, st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
@@ -988,7 +1017,107 @@ struct akr_hip_ctx {
         if (bad == kMappedSentinel) throw std::runtime_error("film check: the device never reported its result");
         if (bad != 0)
             throw std::runtime_error("film check: " + std::to_string(bad) + " of " + std::to_string(N) +
-                                     " pixels do not hold " + std::to_string(spp) + " samples");
+                                     " pixels do not hold " +
+                                     (per_slot ? std::string("their expected") : std::to_string(spp)) + " samples");
+    }
+
+    // ---- subset passes
+    // The ascending list of the slots whose mask byte is non-zero into d_active: per-wave ballot counts,
+    // their exclusive scan, the scatter.  Returns the list's length (the one host wait of a pass: 4 bytes).
+    uint32_t compact_mask(const uint8_t *mask, uint32_t N, hipStream_t st) {
+        if (N == 0) return 0;
+        const uint32_t n_waves = (N + 63u) / 64u;
+        d_active.reserve(N);
+        d_wcount.reserve(n_waves);
+        d_woff.reserve(n_waves);
+        d_nactive.reserve(1);
+        if (d_scan_tmp.n < scan_tmp_bytes(n_waves)) d_scan_tmp.reserve(scan_tmp_bytes(n_waves));
+        timed("compact", st, [&] {
+            launch_mask_count(mask, N, d_wcount.p, st);
+            scan_exclusive_u32(d_scan_tmp.p, d_scan_tmp.n, d_wcount.p, d_woff.p, n_waves, st);
+            launch_mask_compact(mask, N, d_woff.p, d_active.p, d_nactive.p, st);
+        });
+        HIPCHK(hipGetLastError());
+        uint32_t m = 0;
+        HIPCHK(hipMemcpyAsync(&m, d_nactive.p, sizeof(m), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (m > N) throw std::runtime_error("slot mask compaction: " + std::to_string(m) + " active of " + std::to_string(N));
+        return m;
+    }
+
+    // smallest and largest expected count of the slots in d_active[0..m) (list) or of all N slots
+    void count_range(bool list, uint32_t n, hipStream_t st, uint32_t &lo, uint32_t &hi) {
+        d_crange.reserve(2);
+        const uint32_t init[2] = {0xFFFFFFFFu, 0u};
+        HIPCHK(hipMemcpyAsync(d_crange.p, init, sizeof(init), hipMemcpyHostToDevice, st));
+        launch_count_range(d_count.p, list ? d_active.p : nullptr, n, d_crange.p, st);
+        uint32_t out[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(out, d_crange.p, sizeof(out), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        lo = out[0];
+        hi = out[1];
+    }
+
+    // spp more samples for the m slots listed in d_active (ascending), on `st`; updates the session's
+    // counts.  m == N keeps a uniform session uniform.  `range`: recompute spp_min / spp_done of a
+    // non-uniform session from the counts (the adaptive loop knows them and passes false).
+    void render_subset(int32_t spp, uint32_t m, hipStream_t st, bool range = true) {
+        Session &s = session;
+        const uint64_t N = require_session().n;
+        if (m == 0 || spp == 0) return;
+        if (m > N) throw std::runtime_error("render session: more active slots than slots");
+        // the 2^24 cap applies to the largest resulting count; refused before anything changes
+        if (s.uniform) {
+            if ((int64_t)s.spp_done + spp > kSessionSppCap) throw_cap(s.spp_done, spp);
+        } else if ((int64_t)s.spp_done + spp > kSessionSppCap) {  // near the cap only: the largest count among the listed slots
+            uint32_t lo, hi;
+            count_range(true, m, st, lo, hi);
+            if ((int64_t)hi + spp > kSessionSppCap) throw_cap((int32_t)hi, spp);
+        }
+        akr_pt_params p{};
+        p.spp = spp;
+        p.max_depth = s.max_depth;
+        p.ray_clamp = s.ray_clamp;
+        p.flags = s.flags;
+        if (!s.seeded) {  // no sample drawn yet: the slots left out keep their start state x + y * width
+            launch_init_seed(d_pixel.p, (uint32_t)N, cam.width, d_seed.p, st);
+            s.seeded = true;
+        }
+        if (m == N) {
+            render(p, nullptr, 0, st, true);
+        } else {
+            if (s.uniform) {
+                d_count.reserve(N);
+                launch_fill_u32(d_count.p, (uint32_t)N, (uint32_t)s.spp_done, st);
+            }
+            render(p, nullptr, 0, st, true, d_active.p, m);
+        }
+        if (s.uniform && m == N) {
+            s.spp_done += spp;
+            s.spp_min = s.spp_done;
+            return;
+        }
+        launch_count_add(d_count.p, m == N ? nullptr : d_active.p, m, (uint32_t)spp, st);
+        HIPCHK(hipGetLastError());
+        if (s.uniform) {
+            s.uniform = false;
+            s.spp_min = s.spp_done;
+            s.spp_done += spp;
+        } else if (range) {
+            uint32_t lo, hi;
+            count_range(false, (uint32_t)N, st, lo, hi);
+            s.spp_min = (int32_t)lo;
+            s.spp_done = (int32_t)hi;
+        }
+    }
+    static constexpr int32_t kSessionSppCap = 1 << 24;  // a slot's weight is an f32 count of its samples: exact up to 2^24
+    // a call refused before anything changed: the session stays as it was
+    struct Refused : std::runtime_error {
+        using std::runtime_error::runtime_error;
+    };
+    [[noreturn]] static void throw_cap(int32_t have, int32_t spp) {
+        throw Refused("render session: " + std::to_string(have) + " + " + std::to_string(spp) +
+                                 " samples per slot exceed 2^24 (the weight is an f32 count)");
     }
 
     // host waits for both internal streams (before a DMA read-back of the film)
@@ -1025,7 +1154,10 @@ struct akr_hip_ctx {
 
     // cont: p.spp more samples for every slot of the session: the slots, their film sums
     // and (when the session is seeded) their sampler states are the ones the last segment left
-    uint64_t render(const akr_pt_params &p, const akr_rect *tiles, int32_t n_tiles, hipStream_t st, bool cont = false) {
+    // subset (with cont): the pass draws its samples for the n_subset slots listed there only (a masked
+    // continue): the same launches over a shorter fetch list, unranked
+    uint64_t render(const akr_pt_params &p, const akr_rect *tiles, int32_t n_tiles, hipStream_t st, bool cont = false,
+                    const uint32_t *subset = nullptr, uint64_t n_subset = 0) {
         if (p.spp < 0 || p.max_depth < 0) throw std::runtime_error("spp and max_depth must be >= 0");
         if (p.max_depth > 1000) throw std::runtime_error("max_depth too large");
         // counters per pass, each on its own 128-B line (atomics on one line serialise):
@@ -1042,6 +1174,8 @@ struct akr_hip_ctx {
         const bool resume = cont && require_session().seeded;  // else every slot starts from x + y * width
         const uint64_t N = cont ? resume_pixels(n_count_words, st) : setup_pixels(tiles, n_tiles, n_count_words, st);
         if (N == 0) return 0;
+        if (subset && (!cont || n_subset == 0 || n_subset > N)) throw std::runtime_error("render: invalid slot subset");
+        const uint64_t M = subset ? n_subset : N;  // the slots this pass fetches
         if (unchecked_render) {  // a fault raised by an earlier render_device that ran without "verify"
             unchecked_render = false;
             if (done_recorded) HIPCHK(hipEventSynchronize(ev_done));
@@ -1064,7 +1198,7 @@ struct akr_hip_ctx {
         // auto: the persistent kernel for scenes whose shading is constant Diffuse / Emissive; Glossy,
         // Mix or image textures diverge inside the traversal waves, and the wavefront's separate shade
         // kernel measured faster there (textured hall 11.5 vs 16.0 ms per 4K spp)
-        const bool use_path = path_kernel == 1 || (path_kernel == 2 && (int64_t)N <= path_auto_pixels &&
+        const bool use_path = path_kernel == 1 || (path_kernel == 2 && (int64_t)M <= path_auto_pixels &&
                                                    (simple_shading || path_auto_complex));
         if (use_path && tight && wide && trace_args(nullptr).lean) {
             if (p.spp > 0) {
@@ -1076,7 +1210,7 @@ struct akr_hip_ctx {
                 pa.pixel = d_pixel.p;
                 pa.film = d_film.p;
                 pa.work = d_counts.p;
-                pa.n_pix = (uint32_t)N;
+                pa.n_pix = (uint32_t)M;
                 pa.spp = (uint32_t)p.spp;
                 pa.max_depth = p.max_depth;
                 pa.ray_clamp = p.ray_clamp;
@@ -1107,7 +1241,7 @@ struct akr_hip_ctx {
                 // pixels per resident lane of k_path (the occupancy query's grid)
                 const uint64_t lanes = std::max<uint64_t>(1, (uint64_t)path_grid[PATH_PLAIN][tab] *
                                                                  (uint64_t)path_grid_pct / 100) * kTraceBlock;
-                const int64_t ppl1000 = (int64_t)((N * 1000 + lanes / 2) / lanes);
+                const int64_t ppl1000 = (int64_t)((M * 1000 + lanes / 2) / lanes);
                 last_ppl1000 = ppl1000;
                 last_pilot_rays = last_pilot_steps = -1;
                 form_pending = pilot_sum_pending = false;
@@ -1123,7 +1257,7 @@ struct akr_hip_ctx {
                 pa.min_wait = (uint32_t)(path_min_wait > 0 ? path_min_wait : 40);
                 const bool forced = path_spec == 1 || path_defer != 2;
                 // the pilot can rank pixels for every form (path_order 2), or for k_path only (1)
-                const bool pilot = path_order != 0 && p.spp >= order_min_spp && N >= 2 &&
+                const bool pilot = path_order != 0 && !subset && p.spp >= order_min_spp && N >= 2 &&
                                    (path_order == 2 || (!forced || (path_spec != 1 && path_defer == 0)));
                 // a continued render ranks by the camera-ray pilot: the path pilot renders into the film
                 const bool path_pilot = pilot && path_order_pilot_spp > 0 && !cont;
@@ -1158,11 +1292,17 @@ struct akr_hip_ctx {
                 auto configure = [&](int k, PathArgs &x) {
                     const uint64_t resident = (uint64_t)path_grid[k][tab] * (uint64_t)path_grid_pct / 100;
                     const uint32_t grid = (uint32_t)std::max<uint64_t>(
-                        1, std::min<uint64_t>(resident, (N + kTraceBlock - 1) / kTraceBlock));
+                        1, std::min<uint64_t>(resident, (M + kTraceBlock - 1) / kTraceBlock));
                     if (k == PATH_DEFER) {
                         d_contrib.reserve((size_t)18 * grid * kTraceBlock);  // 16 NEE slots + the waiting ray
                         x.contrib = d_contrib.p;
                         x.mix = path_mix ? 1u : 0u;
+                    }
+                    if (subset) {  // the active list in ascending order (k_path_defer keeps its scramble)
+                        x.order = subset;
+                        x.order_mode = k == PATH_DEFER && path_mix ? 1u : 0u;  // FETCH_SCRAMBLE / FETCH_LINEAR
+                        x.prio = 0u;
+                        return grid;
                     }
                     if (x.order && !(k == PATH_PLAIN || path_order == 2)) x.order = nullptr;  // path_order 1
                     if (x.order) {
@@ -1208,7 +1348,10 @@ struct akr_hip_ctx {
                     HIPCHK(hipGetLastError());
                     last_form = form_of(kind);
                 }
-                last_ordered = pa.order ? 1 : 0;
+                last_ordered = pa.order && !subset ? 1 : 0;
+                // a subset pass wrote the probe of its slots only: the others keep the state they had
+                if (subset && probe_p)
+                    launch_probe_fill(d_seed.p, (uint32_t)N, probe_p, AKR_PROBE_SEED | (count ? AKR_PROBE_RAYS : 0u), ms);
             }
             last_passes = 1;
             join_streams(st);
@@ -1223,7 +1366,7 @@ struct akr_hip_ctx {
             const int order_min_spp = (int64_t)N <= path_order_share_pixels
                                           ? std::min(path_order_share_min_spp, path_order_min_spp)
                                           : path_order_min_spp;
-            if (wave_order && path_order != 0 && p.spp >= order_min_spp && N >= 2) {
+            if (wave_order && path_order != 0 && !subset && p.spp >= order_min_spp && N >= 2) {
                 if (!order_warm) {
                     pixel_order((uint32_t)std::min<uint64_t>(N, 64), ms);
                     order_warm = true;
@@ -1244,9 +1387,9 @@ struct akr_hip_ctx {
             // L[ps] and the counter set were last used by pass s - 2, whose splat ends its side-stream work
             if (s >= 2) HIPCHK(hipStreamWaitEvent(ms, ev_splat[ps], 0));
             HIPCHK(hipMemsetAsync(cnt, 0, n_count_words * sizeof(uint32_t), ms));
-            RaygenArgs rg = raygen_args((uint32_t)N, L, qcount(0), s == 0 && !resume);
+            RaygenArgs rg = raygen_args((uint32_t)M, L, qcount(0), s == 0 && !resume);
             rg.probe = probe_p;
-            rg.order = worder;
+            rg.order = subset ? subset : worder;
             timed("raygen", ms, [&] { launch_raygen(rg, ms); });
             for (int b = 0; b < nb; b++, g++) {
                 const bool odd = b & 1;
@@ -1255,7 +1398,7 @@ struct akr_hip_ctx {
                 t.rays = odd ? d_ray1.p : d_ray0.p;
                 t.count = qcount(b);
                 t.hits = d_hit.p;
-                timed("trace_closest", ms, [&] { trace_launch(TRACE_CLOSEST, tight, t, N, ms); });
+                timed("trace_closest", ms, [&] { trace_launch(TRACE_CLOSEST, tight, t, M, ms); });
                 // shade refills shadow queue g % 2: the shadow trace of bounce g - 2 must be done
                 if (g >= 2) HIPCHK(hipStreamWaitEvent(ms, ev_shadow[sq], 0));
                 ShadeArgs sh{};
@@ -1278,7 +1421,7 @@ struct akr_hip_ctx {
                 sh.max_depth = p.max_depth;
                 sh.last = b == nb - 1;
                 sh.probe = probe_p;
-                timed("shade", ms, [&] { launch_shade(sh, (uint32_t)N, ms); });
+                timed("shade", ms, [&] { launch_shade(sh, (uint32_t)M, ms); });
                 HIPCHK(hipEventRecord(ev_shade[sq], ms));
                 HIPCHK(hipStreamWaitEvent(side, ev_shade[sq], 0));
                 if (b < p.max_depth) {
@@ -1290,7 +1433,7 @@ struct akr_hip_ctx {
                     ts.L = L;
                     // option serial_shadow (measurement): on the main stream, so the launch is timed alone
                     hipStream_t sst = serial_shadow ? ms : side;
-                    timed("trace_shadow", sst, [&] { trace_launch(TRACE_SHADOW, tight, ts, N, sst); });
+                    timed("trace_shadow", sst, [&] { trace_launch(TRACE_SHADOW, tight, ts, M, sst); });
                 }
                 if (serial_shadow) {
                     HIPCHK(hipEventRecord(ev_shadow[sq], ms));
@@ -1304,9 +1447,10 @@ struct akr_hip_ctx {
             SplatArgs sp{};
             sp.L = L;
             sp.film = d_film.p;
-            sp.n = (uint32_t)N;
+            sp.n = (uint32_t)M;
             sp.ray_clamp = p.ray_clamp;
-            timed("splat", side, [&] { launch_splat(sp, (uint32_t)N, side); });
+            sp.order = subset;
+            timed("splat", side, [&] { launch_splat(sp, (uint32_t)M, side); });
             HIPCHK(hipEventRecord(ev_splat[ps], side));
         }
         // the last shade of every pass ran on the main stream and left each slot's sampler state
@@ -2022,7 +2166,8 @@ int akr_hip_render_node(akr_hip_ctx *const *ctxs, int32_t n_ctx, const akr_pt_pa
 
 namespace {
 // Film::merge_tile (core/film.h:85-95) of the context's packed film into full-frame host buffers
-void merge_film(akr_hip_ctx *ctx, uint64_t N, int spp, float *radiance, float *weight) {
+// (per_slot: a session whose slots hold different counts, checked against its per-slot counts)
+void merge_film(akr_hip_ctx *ctx, uint64_t N, int spp, float *radiance, float *weight, bool per_slot = false) {
     hipStream_t st = ctx->stream;
     if (N == 0) {
         ctx->mark_done(st);
@@ -2034,16 +2179,22 @@ void merge_film(akr_hip_ctx *ctx, uint64_t N, int spp, float *radiance, float *w
     ctx->host_join();
     HIPCHK(hipStreamSynchronize(st));
     ctx->check_fault();
-    ctx->verify_weights(st, N, spp);
+    ctx->verify_weights(st, N, spp, per_slot);
     std::vector<float4> film(N);
+    std::vector<uint32_t> counts;
+    if (per_slot && ctx->verify) {
+        counts.resize(N);
+        HIPCHK(hipMemcpyAsync(counts.data(), ctx->d_count.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipMemcpyAsync(film.data(), ctx->d_film.p, N * sizeof(float4), hipMemcpyDeviceToHost, st));
     ctx->mark_done(st);
     HIPCHK(hipStreamSynchronize(st));
     if (ctx->verify) {  // the read-back itself: every copied slot holds spp samples
         uint64_t bad = 0;
-        for (uint64_t k = 0; k < N; k++) bad += film[k].w != (float)spp;
+        for (uint64_t k = 0; k < N; k++) bad += film[k].w != (float)(per_slot ? counts[k] : (uint32_t)spp);
         if (bad) throw std::runtime_error("film read-back: " + std::to_string(bad) + " of " + std::to_string(N) +
-                                          " pixels do not hold " + std::to_string(spp) + " samples");
+                                          " pixels do not hold " +
+                                          (per_slot ? std::string("their expected") : std::to_string(spp)) + " samples");
     }
     const int W = ctx->cam.width;
     const std::vector<uint32_t> &pl = ctx->host_pixels();
@@ -2093,7 +2244,7 @@ int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const a
 }
 
 namespace {
-constexpr int32_t kMaxSessionSpp = 1 << 24;  // a slot's weight is an f32 count of its samples: exact up to 2^24
+constexpr int32_t kMaxSessionSpp = akr_hip_ctx::kSessionSppCap;
 
 // The session's parameters with `spp` more samples, checked
 akr_pt_params continue_params(akr_hip_ctx *ctx, int32_t spp) {
@@ -2119,10 +2270,13 @@ int akr_hip_render_continue(akr_hip_ctx *ctx, int32_t spp, float *radiance, floa
         try {
             if (spp > 0) {
                 ctx->render(p, nullptr, 0, ctx->stream, true);
+                if (!s.uniform) launch_count_add(ctx->d_count.p, nullptr, (uint32_t)s.n, (uint32_t)spp, ctx->stream);
                 s.spp_done += spp;
+                s.spp_min += spp;
                 s.seeded = true;
+                s.ad.on = false;
             }
-            merge_film(ctx, s.n, s.spp_done, radiance, weight);
+            merge_film(ctx, s.n, s.spp_done, radiance, weight, !s.uniform);
         } catch (...) {  // a segment that fails leaves no session: its film may be partly extended
             ctx->drop_session();
             throw;
@@ -2142,15 +2296,18 @@ int akr_hip_render_continue_device(akr_hip_ctx *ctx, int32_t spp, float *d_radia
         try {
             if (spp > 0) {
                 ctx->render(p, nullptr, 0, st, true);
+                if (!s.uniform) launch_count_add(ctx->d_count.p, nullptr, (uint32_t)N, (uint32_t)spp, st);
                 s.spp_done += spp;
+                s.spp_min += spp;
                 s.seeded = true;
+                s.ad.on = false;
             } else {
                 ctx->serialize(st);
             }
             if (n_pixels) *n_pixels = N;
             ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)N, d_radiance, d_weight, st); });
             HIPCHK(hipGetLastError());
-            ctx->verify_weights(st, N, s.spp_done);
+            ctx->verify_weights(st, N, s.spp_done, !s.uniform);
             if (spp > 0) ctx->unchecked_render = !ctx->verify;
             ctx->mark_done(st);
         } catch (...) {
@@ -2158,6 +2315,287 @@ int akr_hip_render_continue_device(akr_hip_ctx *ctx, int32_t spp, float *d_radia
             throw;
         }
         ctx->session = s;
+    });
+}
+
+namespace {
+// the session's totals to the caller: host form (added into full-frame buffers) or device form (packed)
+void session_film_host(akr_hip_ctx *ctx, float *radiance, float *weight) {
+    const akr_hip_ctx::Session &s = ctx->session;
+    merge_film(ctx, s.n, s.spp_done, radiance, weight, !s.uniform);
+}
+void session_film_device(akr_hip_ctx *ctx, float *d_radiance, float *d_weight, hipStream_t st, bool rendered) {
+    const akr_hip_ctx::Session &s = ctx->session;
+    ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)s.n, d_radiance, d_weight, st); });
+    HIPCHK(hipGetLastError());
+    ctx->verify_weights(st, s.n, s.spp_done, !s.uniform);
+    if (rendered) ctx->unchecked_render = !ctx->verify;
+    ctx->mark_done(st);
+}
+
+// spp more samples for the slots whose byte of the device mask is set
+void continue_masked(akr_hip_ctx *ctx, int32_t spp, const uint8_t *d_mask, uint64_t n, hipStream_t st) {
+    const akr_hip_ctx::Session &s = ctx->require_session();
+    if (spp < 0) throw std::runtime_error("spp must be >= 0");
+    if (n != s.n)
+        throw std::runtime_error("masked continue: the mask has " + std::to_string(n) + " bytes, the session has " +
+                                 std::to_string(s.n) + " slots");
+    if (n && !d_mask) throw std::runtime_error("null argument");
+    ctx->serialize(st);
+    if (spp == 0 || n == 0) return;
+    ctx->session.ad.on = false;
+    const uint32_t m = ctx->compact_mask(d_mask, (uint32_t)n, st);
+    ctx->render_subset(spp, m, st);
+}
+}  // namespace
+
+int akr_hip_render_continue_masked(akr_hip_ctx *ctx, int32_t spp, const uint8_t *mask, uint64_t n, float *radiance,
+                                   float *weight) {
+    return guard(ctx, [&] {
+        if (!radiance || !weight) throw std::runtime_error("null argument");
+        const akr_hip_ctx::Session &s = ctx->require_session();
+        if (spp < 0) throw std::runtime_error("spp must be >= 0");
+        if (n != s.n)
+            throw std::runtime_error("masked continue: the mask has " + std::to_string(n) + " bytes, the session has " +
+                                     std::to_string(s.n) + " slots");
+        if (n && !mask) throw std::runtime_error("null argument");
+        hipStream_t st = ctx->stream;
+        const akr_hip_ctx::Session before = ctx->session;
+        bool rendering = false;
+        try {
+            if (n) {
+                ctx->serialize(st);
+                ctx->d_mask.upload(mask, n, st);
+            }
+            rendering = true;
+            continue_masked(ctx, spp, ctx->d_mask.p, n, st);
+            session_film_host(ctx, radiance, weight);
+        } catch (const akr_hip_ctx::Refused &) {  // the cap: nothing changed
+            ctx->session = before;
+            throw;
+        } catch (...) {  // a pass that fails while rendering ends the session
+            if (rendering) ctx->drop_session();
+            throw;
+        }
+    });
+}
+
+int akr_hip_render_continue_masked_device(akr_hip_ctx *ctx, int32_t spp, const uint8_t *d_mask, uint64_t n,
+                                          float *d_radiance, float *d_weight, void *stream, uint64_t *n_pixels) {
+    return guard(ctx, [&] {
+        if (!d_radiance || !d_weight) throw std::runtime_error("null argument");
+        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        const akr_hip_ctx::Session before = ctx->require_session();
+        if (spp < 0) throw std::runtime_error("spp must be >= 0");
+        if (n != before.n)
+            throw std::runtime_error("masked continue: the mask has " + std::to_string(n) + " bytes, the session has " +
+                                     std::to_string(before.n) + " slots");
+        try {
+            continue_masked(ctx, spp, d_mask, n, st);
+            if (n_pixels) *n_pixels = before.n;
+            session_film_device(ctx, d_radiance, d_weight, st, spp > 0);
+        } catch (const akr_hip_ctx::Refused &) {  // the cap: nothing changed
+            ctx->session = before;
+            throw;
+        } catch (...) {
+            ctx->drop_session();
+            throw;
+        }
+    });
+}
+
+int akr_hip_render_state_spp_range(akr_hip_ctx *ctx, int32_t *spp_min, int32_t *spp_max) {
+    return guard(ctx, [&] {
+        const akr_hip_ctx::Session &s = ctx->require_session();
+        if (spp_min) *spp_min = s.uniform ? s.spp_done : s.spp_min;
+        if (spp_max) *spp_max = s.spp_done;
+    });
+}
+
+namespace {
+void check_adaptive(const akr_pt_params *params, const akr_adaptive_params *ap) {
+    if (!params || !ap) throw std::runtime_error("null argument");
+    if (params->spp < 0 || params->max_depth < 0) throw std::runtime_error("spp and max_depth must be >= 0");
+    if (ap->min_spp < 1) throw std::runtime_error("adaptive render: min_spp must be >= 1");
+    if (ap->pass_spp < 0) throw std::runtime_error("adaptive render: pass_spp must be >= 0");
+    if (!(ap->threshold >= 0.0f)) throw std::runtime_error("adaptive render: threshold must be >= 0 and not NaN");
+    if (params->spp > akr_hip_ctx::kSessionSppCap) throw std::runtime_error("adaptive render: the cap exceeds 2^24 samples");
+}
+
+// The adaptive loop in two pieces, both on `st`.  adaptive_begin: min_spp for every
+// slot (this starts the session) and the snapshot.  adaptive_step: one pass over the active strips and
+// its test.  The run's state lives in the session (Session::ad); ad.more says whether a step remains.
+uint64_t adaptive_begin(akr_hip_ctx *ctx, const akr_pt_params &params, const akr_adaptive_params &ap,
+                        const akr_rect *tiles, int32_t n_tiles, hipStream_t st) {
+    const int32_t cap = params.spp;
+    akr_pt_params p0 = params;
+    p0.spp = std::min(cap, ap.min_spp);
+    const uint64_t N = ctx->render(p0, tiles, n_tiles, st);
+    ctx->open_session(p0, N, p0.spp, p0.spp > 0);
+    const uint64_t n_strips = (N + 63) / 64;
+    akr_hip_ctx::Session::Adaptive &ad = ctx->session.ad;
+    ad = akr_hip_ctx::Session::Adaptive{};
+    ad.on = true;
+    ad.cap = cap;
+    ad.pass_spp = ap.pass_spp;
+    ad.threshold = ap.threshold;
+    ad.total = p0.spp;
+    ad.m = (uint32_t)N;
+    akr_adaptive_info &out = ad.info;
+    out.passes = 1;
+    out.spp_min = out.spp_max = p0.spp;
+    out.samples = N * (uint64_t)p0.spp;
+    out.strips = n_strips;
+    ad.more = cap > ap.min_spp && N > 0;
+    if (ad.more) {
+        // the first pass is complete on the host before its film is copied (as merge_film waits before
+        // its read-back); then the snapshot, every strip active, every slot masked
+        ctx->host_join();
+        HIPCHK(hipStreamSynchronize(st));
+        ctx->check_fault();
+        ctx->d_prev.reserve(N);
+        ctx->d_mask.reserve(N);
+        ctx->d_strip_active.reserve(n_strips);
+        ctx->d_strip_err.reserve(n_strips);
+        HIPCHK(hipMemcpyAsync(ctx->d_prev.p, ctx->d_film.p, N * sizeof(float4), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(ctx->d_mask.p, 1, N, st));
+        HIPCHK(hipMemsetAsync(ctx->d_strip_active.p, 1, n_strips, st));
+        HIPCHK(hipMemsetAsync(ctx->d_strip_err.p, 0, n_strips * sizeof(float), st));
+        ctx->session.n_strips = n_strips;
+    }
+    return N;
+}
+
+void adaptive_step(akr_hip_ctx *ctx, hipStream_t st) {
+    akr_hip_ctx::Session &s = ctx->session;
+    akr_hip_ctx::Session::Adaptive &ad = s.ad;
+    if (!ctx->require_session().ad.on)
+        throw std::runtime_error("adaptive step: the session is not an adaptive render in progress "
+                                 "(start one with akr_hip_adaptive_begin; a continue with samples ends it)");
+    if (!ad.more) return;
+    const uint32_t N = (uint32_t)s.n;
+    akr_adaptive_info &out = ad.info;
+    // every active strip holds ad.total samples; the pass is clipped at the cap
+    const int64_t want = ad.pass_spp > 0 ? (int64_t)ad.total + ad.pass_spp : 2 * (int64_t)ad.total;
+    const int32_t step = (int32_t)(std::min<int64_t>(want, ad.cap) - ad.total);
+    ctx->render_subset(step, ad.m, st, false);
+    ad.total += step;
+    out.passes++;
+    out.samples += (uint64_t)ad.m * (uint64_t)step;
+    ctx->timed("adaptive_test", st, [&] {
+        launch_adaptive_test(ctx->d_film.p, ctx->d_prev.p, N, ad.threshold, ctx->d_strip_err.p, ctx->d_strip_active.p,
+                             ctx->d_mask.p, st);
+    });
+    HIPCHK(hipGetLastError());
+    const uint32_t before = ad.m;
+    ad.m = ctx->compact_mask(ctx->d_mask.p, N, st);  // the pass's one host read: the active count
+    if (!ad.some_stopped) {  // no strip had stopped before this test: the smallest count follows the total
+        out.spp_min = ad.total;
+        if (ad.m < before) ad.some_stopped = true;
+    }
+    out.spp_max = ad.total;
+    s.spp_done = out.spp_max;
+    s.spp_min = out.spp_min;
+    ad.more = ad.m > 0 && ad.total < ad.cap;
+    // strips are 64 slots, but for a short last one
+    out.strips_at_cap = ad.total >= ad.cap ? ((uint64_t)ad.m + 63) / 64 : 0;
+}
+
+uint64_t render_adaptive(akr_hip_ctx *ctx, const akr_pt_params &params, const akr_adaptive_params &ap,
+                         const akr_rect *tiles, int32_t n_tiles, hipStream_t st, akr_adaptive_info *info) {
+    const uint64_t N = adaptive_begin(ctx, params, ap, tiles, n_tiles, st);
+    while (ctx->session.ad.more) adaptive_step(ctx, st);
+    if (info) *info = ctx->session.ad.info;
+    return N;
+}
+}  // namespace
+
+int akr_hip_adaptive_begin(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_adaptive_params *ap,
+                           const akr_rect *tiles, int32_t n_tiles, akr_adaptive_info *info, int32_t *more) {
+    return guard(ctx, [&] {
+        check_adaptive(params, ap);
+        hipStream_t st = ctx->stream;
+        try {
+            adaptive_begin(ctx, *params, *ap, tiles, n_tiles, st);
+            const akr_hip_ctx::Session &s = ctx->session;
+            ctx->verify_weights(st, s.n, s.spp_done);
+            ctx->mark_done(st);
+        } catch (...) {
+            ctx->drop_session();
+            throw;
+        }
+        if (info) *info = ctx->session.ad.info;
+        if (more) *more = ctx->session.ad.more ? 1 : 0;
+    });
+}
+
+int akr_hip_adaptive_step(akr_hip_ctx *ctx, akr_adaptive_info *info, int32_t *more) {
+    return guard(ctx, [&] {
+        if (!ctx->require_session().ad.on) adaptive_step(ctx, ctx->stream);  // throws the message
+        hipStream_t st = ctx->stream;
+        try {
+            ctx->serialize(st);
+            adaptive_step(ctx, st);
+            const akr_hip_ctx::Session &s = ctx->session;
+            ctx->verify_weights(st, s.n, s.spp_done, !s.uniform);
+            ctx->mark_done(st);
+        } catch (...) {
+            ctx->drop_session();
+            throw;
+        }
+        if (info) *info = ctx->session.ad.info;
+        if (more) *more = ctx->session.ad.more ? 1 : 0;
+    });
+}
+
+int akr_hip_render_adaptive(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_adaptive_params *ap,
+                            const akr_rect *tiles, int32_t n_tiles, float *radiance, float *weight,
+                            akr_adaptive_info *info) {
+    return guard(ctx, [&] {
+        check_adaptive(params, ap);
+        if (!radiance || !weight) throw std::runtime_error("null argument");
+        try {
+            render_adaptive(ctx, *params, *ap, tiles, n_tiles, ctx->stream, info);
+            session_film_host(ctx, radiance, weight);
+        } catch (...) {
+            ctx->drop_session();
+            throw;
+        }
+    });
+}
+
+int akr_hip_render_adaptive_device(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_adaptive_params *ap,
+                                   const akr_rect *tiles, int32_t n_tiles, float *d_radiance, float *d_weight,
+                                   void *stream, uint64_t *n_pixels, akr_adaptive_info *info) {
+    return guard(ctx, [&] {
+        check_adaptive(params, ap);
+        if (!d_radiance || !d_weight) throw std::runtime_error("null argument");
+        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        try {
+            const uint64_t N = render_adaptive(ctx, *params, *ap, tiles, n_tiles, st, info);
+            if (n_pixels) *n_pixels = N;
+            session_film_device(ctx, d_radiance, d_weight, st, true);
+        } catch (...) {
+            ctx->drop_session();
+            throw;
+        }
+    });
+}
+
+int akr_hip_adaptive_error(akr_hip_ctx *ctx, float *strip_error, uint8_t *strip_active, uint64_t n_strips) {
+    return guard(ctx, [&] {
+        const akr_hip_ctx::Session &s = ctx->require_session();
+        if (s.n_strips == 0) throw std::runtime_error("adaptive error: the session ran no convergence test");
+        if (n_strips != s.n_strips)
+            throw std::runtime_error("adaptive error: n_strips is " + std::to_string(n_strips) + ", the session has " +
+                                     std::to_string(s.n_strips) + " strips");
+        if (!strip_error || !strip_active) throw std::runtime_error("null argument");
+        hipStream_t st = ctx->stream;
+        ctx->serialize(st);
+        HIPCHK(hipMemcpyAsync(strip_error, ctx->d_strip_err.p, n_strips * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(strip_active, ctx->d_strip_active.p, n_strips, hipMemcpyDeviceToHost, st));
+        ctx->mark_done(st);
+        HIPCHK(hipStreamSynchronize(st));
     });
 }
 

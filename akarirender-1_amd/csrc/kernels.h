@@ -43,4 +43,20 @@ size_t pixel_order_tmp_bytes(uint32_t n);
 void sort_pixel_order(void *tmp, size_t tmp_bytes, const uint32_t *key_in, uint32_t *key_out, const uint32_t *idx_in,
                       uint32_t *idx_out, uint32_t n, hipStream_t st);
 
+// adaptive sampling: mask -> ascending list of active slots (per-wave counts, their
+// exclusive scan by rocPRIM in lbvh.hip, the scatter), per-slot expected counts, the convergence test
+void launch_mask_count(const uint8_t *mask, uint32_t n, uint32_t *wcount, hipStream_t st);
+size_t scan_tmp_bytes(uint32_t n);
+void scan_exclusive_u32(void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, uint32_t n, hipStream_t st);
+void launch_mask_compact(const uint8_t *mask, uint32_t n, const uint32_t *woff, uint32_t *list, uint32_t *total,
+                         hipStream_t st);
+void launch_fill_u32(uint32_t *p, uint32_t n, uint32_t v, hipStream_t st);
+void launch_count_add(uint32_t *count, const uint32_t *list, uint32_t n, uint32_t spp, hipStream_t st);
+void launch_check_counts(const float4 *film, const uint32_t *count, uint32_t n, uint32_t *bad, hipStream_t st);
+void launch_count_range(const uint32_t *count, const uint32_t *list, uint32_t n, uint32_t *out, hipStream_t st);
+void launch_init_seed(const uint32_t *pixel, uint32_t n, int32_t width, uint32_t *seed, hipStream_t st);
+void launch_probe_fill(const uint32_t *seed, uint32_t n, uint4 *probe, uint32_t flags, hipStream_t st);
+void launch_adaptive_test(const float4 *film, float4 *prev, uint32_t n, float threshold, float *strip_err,
+                          uint8_t *strip_active, uint8_t *mask, hipStream_t st);
+
 }  // namespace akr

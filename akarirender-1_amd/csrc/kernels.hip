@@ -2861,6 +2861,130 @@ __global__ void k_store_word(const uint32_t *src, uint32_t *dst) {
     }
 }
 
+// ------------------------------------------------------------------------- adaptive sampling
+// Subset passes and the convergence test.  Every kernel here runs one thread per
+// film slot in packed tile order; kBlock is a multiple of the wave size, so a wave covers slots
+// [64 k, 64 k + 64): one strip.
+static_assert(kBlock % 64 == 0, "a wave of these kernels is one strip of 64 slots");
+
+// Compaction, step 1: the active slots of each wave (ballot + popcount), one word per wave
+__global__ __launch_bounds__(kBlock) void k_mask_count(const uint8_t *mask, uint32_t n, uint32_t *wcount) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if ((i & ~63u) >= n) return;  // wave-uniform
+    const unsigned long long m = __ballot(i < n && mask[i] != 0);
+    if (__lane_id() == 0) wcount[i >> 6] = (uint32_t)__popcll(m);
+}
+
+// Compaction, step 2 (after the exclusive scan of the wave counts): each active slot to its place in
+// the ascending list; the last wave writes the list's length
+__global__ __launch_bounds__(kBlock) void k_mask_compact(const uint8_t *mask, uint32_t n, const uint32_t *woff,
+                                                        uint32_t *list, uint32_t *total) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if ((i & ~63u) >= n) return;  // wave-uniform
+    const bool on = i < n && mask[i] != 0;
+    const unsigned long long m = __ballot(on);
+    const uint32_t base = woff[i >> 6];
+    if (on) list[base + lane_prefix(m)] = i;
+    if (__lane_id() == 0 && (i >> 6) == ((n - 1u) >> 6)) *total = base + (uint32_t)__popcll(m);
+}
+
+__global__ __launch_bounds__(kBlock) void k_fill_u32(uint32_t *p, uint32_t n, uint32_t v) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// a pass's samples onto the expected counts of its slots (`list` null: slots 0..n-1)
+__global__ __launch_bounds__(kBlock) void k_count_add(uint32_t *count, const uint32_t *list, uint32_t n, uint32_t spp) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) count[list ? list[i] : i] += spp;
+}
+
+// k_check_weights for a film whose slots hold different counts
+__global__ __launch_bounds__(kBlock) void k_check_counts(const float4 *film, const uint32_t *count, uint32_t n,
+                                                        uint32_t *bad) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const unsigned long long m = __ballot(i < n && film[i].w != (float)count[i]);
+    if (__lane_id() == 0 && m) atomicAdd(bad, (uint32_t)__popcll(m));
+}
+
+// smallest and largest expected count of the listed slots (`list` null: slots 0..n-1) into
+// out[0] (preset to 0xFFFFFFFF) and out[1] (preset to 0): one atomic pair per wave
+__global__ __launch_bounds__(kBlock) void k_count_range(const uint32_t *count, const uint32_t *list, uint32_t n,
+                                                       uint32_t *out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if ((i & ~63u) >= n) return;  // wave-uniform
+    const uint32_t c = count[list ? list[i < n ? i : n - 1u] : (i < n ? i : n - 1u)];
+    uint32_t lo = c, hi = c;
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor(lo, off));
+        hi = max(hi, (uint32_t)__shfl_xor(hi, off));
+    }
+    if (__lane_id() == 0) {
+        atomicMin(out, lo);
+        atomicMax(out + 1, hi);
+    }
+}
+
+// the start state x + y * width of every slot (a session that has drawn no sample yet)
+__global__ __launch_bounds__(kBlock) void k_init_seed(const uint32_t *pixel, uint32_t n, int32_t width, uint32_t *seed) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t px = pixel[i];
+    seed[i] = (uint32_t)((int)(px & 0xFFFFu) + (int)(px >> 16) * width);
+}
+
+// Pixel probe of a subset pass: the slots the pass did not touch (their record is still zero) hold the
+// sampler state they already had, and no rays
+__global__ __launch_bounds__(kBlock) void k_probe_fill(const uint32_t *seed, uint32_t n, uint4 *probe, uint32_t flags) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (probe[i].w == 0u) probe[i] = make_uint4(seed[i], 0u, 0u, flags);
+}
+
+// The convergence test: one wave per strip, one lane per slot.  For a slot with snapshot P (the film
+// before the pass being judged) and film I, both (r, g, b sums, count), c1 > c0 > 0:
+//   e = (|Ir/c1 - Pr/c0| + |Ig/c1 - Pg/c0| + |Ib/c1 - Pb/c0|) / sqrt(Ir/c1 + Ig/c1 + Ib/c1), 0 where the sum is not > 0
+// f32, left to right, no contraction, correctly rounded / and sqrt.  The strip's error E is the sum of
+// its slots' e as the fixed binary tree of the xor shuffles 1, 2, 4, 8, 16, 32 (absent slots of a short
+// last strip count 0), divided by its slot count.  The strip stops when E <= threshold (tested as
+// !(E <= threshold): NaN keeps sampling).  A strip that goes on has its snapshot refreshed from the
+// film and its slots' mask bytes set; a strip that stops has them cleared, keeps E and is never
+// looked at again.
+__global__ __launch_bounds__(kBlock) void k_adaptive_test(const float4 *film, float4 *prev, uint32_t n, float threshold,
+                                                         float *strip_err, uint8_t *strip_active, uint8_t *mask) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t first = i & ~63u, s = i >> 6;
+    if (first >= n) return;             // wave-uniform
+    if (strip_active[s] == 0) return;   // wave-uniform: stopped earlier
+    const bool have = i < n;
+    float e = 0.0f;
+    float4 I = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (have) {
+        I = film[i];
+        const float4 P = prev[i];
+        const float m1r = I.x / I.w, m1g = I.y / I.w, m1b = I.z / I.w;
+        const float m0r = P.x / P.w, m0g = P.y / P.w, m0b = P.z / P.w;
+        float d = fabsf(m1r - m0r);
+        d += fabsf(m1g - m0g);
+        d += fabsf(m1b - m0b);
+        float sum = m1r + m1g;
+        sum += m1b;
+        e = sum > 0.0f ? d / sqrtf(sum) : 0.0f;
+    }
+    for (int off = 1; off < 64; off <<= 1) e += __shfl_xor(e, off);
+    const uint32_t cnt = min(64u, n - first);
+    const float E = e / (float)cnt;
+    const bool go = !(E <= threshold);
+    if (__lane_id() == 0) {
+        strip_err[s] = E;
+        strip_active[s] = go ? 1 : 0;
+    }
+    if (have) {
+        mask[i] = go ? 1 : 0;
+        if (go) prev[i] = I;
+    }
+}
+
 // ------------------------------------------------------------------------------------ launch
 static inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
@@ -2993,6 +3117,37 @@ void launch_probe_seed(const uint32_t *seed, uint32_t n, uint4 *probe, hipStream
 }
 void launch_expand_pixels(const uint4 *tiles, uint32_t n_tiles, uint32_t n, uint32_t *pixel, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_expand_pixels, dim3(blocks_for(n)), dim3(kBlock), 0, st, tiles, n_tiles, n, pixel);
+}
+void launch_mask_count(const uint8_t *mask, uint32_t n, uint32_t *wcount, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_mask_count, dim3(blocks_for(n)), dim3(kBlock), 0, st, mask, n, wcount);
+}
+void launch_mask_compact(const uint8_t *mask, uint32_t n, const uint32_t *woff, uint32_t *list, uint32_t *total,
+                         hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_mask_compact, dim3(blocks_for(n)), dim3(kBlock), 0, st, mask, n, woff, list, total);
+}
+void launch_fill_u32(uint32_t *p, uint32_t n, uint32_t v, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_fill_u32, dim3(blocks_for(n)), dim3(kBlock), 0, st, p, n, v);
+}
+void launch_count_add(uint32_t *count, const uint32_t *list, uint32_t n, uint32_t spp, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_count_add, dim3(blocks_for(n)), dim3(kBlock), 0, st, count, list, n, spp);
+}
+void launch_check_counts(const float4 *film, const uint32_t *count, uint32_t n, uint32_t *bad, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_check_counts, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, count, n, bad);
+}
+void launch_count_range(const uint32_t *count, const uint32_t *list, uint32_t n, uint32_t *out, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_count_range, dim3(blocks_for(n)), dim3(kBlock), 0, st, count, list, n, out);
+}
+void launch_init_seed(const uint32_t *pixel, uint32_t n, int32_t width, uint32_t *seed, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_init_seed, dim3(blocks_for(n)), dim3(kBlock), 0, st, pixel, n, width, seed);
+}
+void launch_probe_fill(const uint32_t *seed, uint32_t n, uint4 *probe, uint32_t flags, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_probe_fill, dim3(blocks_for(n)), dim3(kBlock), 0, st, seed, n, probe, flags);
+}
+void launch_adaptive_test(const float4 *film, float4 *prev, uint32_t n, float threshold, float *strip_err,
+                          uint8_t *strip_active, uint8_t *mask, hipStream_t st) {
+    if (n)
+        hipLaunchKernelGGL(k_adaptive_test, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, prev, n, threshold, strip_err,
+                           strip_active, mask);
 }
 void launch_unpack(const float4 *film, uint32_t n, float *rad, float *w, hipStream_t st) {
     if (n == 0) return;

@@ -17,6 +17,7 @@
 // so the left child is the lower one along it.  Leaves hold one triangle.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "kernels.h"
 
@@ -370,6 +371,17 @@ void sort_pixel_order(void *tmp, size_t tmp_bytes, const uint32_t *key_in, uint3
     static_assert(kWorkShards <= 8, "the sort key holds the shard in 3 bits");
     LB_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, key_in, key_out, idx_in, idx_out, n, 0,
                                        (int)(kOrderClassBits + 3), st));
+}
+
+// Exclusive scan of the per-wave active counts of a slot mask (adaptive sampling)
+size_t scan_tmp_bytes(uint32_t n) {
+    size_t bytes = 0;
+    LB_CHECK(rocprim::exclusive_scan(nullptr, bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)n,
+                                     rocprim::plus<uint32_t>(), (hipStream_t)0));
+    return bytes;
+}
+void scan_exclusive_u32(void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, uint32_t n, hipStream_t st) {
+    LB_CHECK(rocprim::exclusive_scan(tmp, tmp_bytes, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
 }
 
 }  // namespace akr

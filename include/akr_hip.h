@@ -48,7 +48,8 @@ extern "C" {
 
 /* 2: akr_trace_counts gained deep_rays[3]; akr_pixel_probe / akr_hip_pixel_probe added
  * 3: akr_trace_counts gained leaf_tests[3]
- *    (still 3 with the render session calls below: they only add exports and change no struct layout) */
+ *    (still 3 with the render session and adaptive sampling calls below: they only add exports and
+ *    change no struct layout) */
 #define AKR_HIP_API_VERSION 3
 
 typedef struct akr_hip_ctx akr_hip_ctx;
@@ -337,6 +338,86 @@ int akr_hip_render_state_export(akr_hip_ctx *ctx, uint32_t *sampler, float *film
  * x + y * width, a zero film and spp 0, continued, reproduce a fresh render. */
 int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_rect *tiles,
                                 int32_t n_tiles, const uint32_t *sampler, const float *film, uint64_t n);
+
+/* ---- Sessions whose slots hold different sample counts, and adaptive sampling.
+ *
+ * A masked continue renders `spp` more samples for the slots whose byte in mask[n] (packed tile
+ * order, n = the session's n_pixels) is non-zero and nothing for the others.  A slot's samples are one
+ * LCG chain, so a slot that has received c samples equals the c-spp render at that pixel bit for bit,
+ * whatever its neighbours received.  The mask is compacted on the device into the ascending list of
+ * active slots, and the pass is the usual launch over that shorter list, unranked (the cost order of
+ * §3.10 is not computed for a subset; all orders give the same bits).  The auto form rule sees the
+ * number of active slots as its pixel count.
+ *
+ *  - n != n_pixels is refused and the session stays.  No session: "no render session to continue".
+ *  - An all-zero mask, or spp = 0, renders nothing and returns the totals.
+ *  - The 2^24 cap applies to the largest resulting count; a refused call changes nothing.
+ *  - A later akr_hip_render_continue adds spp to every slot, from each slot's own count.
+ *  - akr_render_state_info.spp_done reports the largest count, akr_hip_render_state_spp_range both ends.
+ *  - akr_hip_render_state_export is unchanged: its film weights are the counts.  akr_hip_render_state_import
+ *    refuses such a film (its weights differ from spp): a non-uniform session cannot be checkpointed.
+ *  - Option "verify" compares every slot's weight with that slot's expected count.
+ *  - Option "pixel_probe": each slot's sampler state after its own total (for slots the mask leaves out,
+ *    the state they already had), and the ray counts of that pass alone. */
+int akr_hip_render_continue_masked(akr_hip_ctx *ctx, int32_t spp, const uint8_t *mask, uint64_t n,
+                                   float *radiance, float *weight);
+int akr_hip_render_continue_masked_device(akr_hip_ctx *ctx, int32_t spp, const uint8_t *d_mask, uint64_t n,
+                                          float *d_radiance, float *d_weight, void *stream,
+                                          uint64_t *n_pixels);
+/* The smallest and the largest sample count of the session's slots (equal for a uniform session). */
+int akr_hip_render_state_spp_range(akr_hip_ctx *ctx, int32_t *spp_min, int32_t *spp_max);
+
+/* Adaptive render: sample until the film has converged, strip by strip.  A strip is 64 consecutive
+ * slots in packed tile order (the last may be short).  Every slot gets min_spp samples; then passes
+ * run over the strips still active (pass_spp more samples each, or with pass_spp 0 as many as the
+ * strip holds, doubling its count), clipped so that no count passes the cap params->spp.  After each
+ * pass the convergence test compares the film I with the snapshot P taken before that pass; per slot,
+ * with counts c1 > c0 > 0, in f32, left to right, unfused, correctly rounded / and sqrt:
+ *     m1 = I / c1, m0 = P / c0 (per channel)
+ *     d = |m1r - m0r| + |m1g - m0g| + |m1b - m0b|,  s = m1r + m1g + m1b,  e = s > 0 ? d / sqrt(s) : 0
+ * The strip error E is the sum of its slots' e as a fixed binary tree (adjacent pairs, six levels;
+ * absent slots of a short strip count 0) divided by the strip's slot count.  A strip stops when
+ * E <= threshold (a NaN keeps sampling) and never restarts; a strip that goes on takes the film as its
+ * new snapshot.  The loop ends when no strip is active or the active strips hold the cap.  All active
+ * strips hold the same count at every moment.  params->spp <= min_spp is a plain render of params->spp
+ * with no test.  The film does not depend on the render form, the cost order or exact_cull.  The
+ * session stays and can be continued, masked or uniformly.  The host reads four bytes per pass (the
+ * number of active slots); the film stays on the device between passes. */
+typedef struct akr_adaptive_params {
+    int32_t min_spp;    /* every slot gets these before the first test, >= 1 */
+    int32_t pass_spp;   /* samples per later pass; 0: each pass doubles the active slots' count */
+    float threshold;    /* >= 0, not NaN */
+    int32_t _pad;
+} akr_adaptive_params;
+typedef struct akr_adaptive_info {
+    int32_t passes;           /* the min_spp pass and every later pass */
+    int32_t spp_min, spp_max, _pad;
+    uint64_t samples;         /* sum of all slots' counts */
+    uint64_t strips, strips_at_cap;   /* strips still above the threshold when they reached params->spp */
+} akr_adaptive_info;
+/* Host form: ADDS the film to full-frame buffers like akr_hip_render.  `info` may be null. */
+int akr_hip_render_adaptive(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_adaptive_params *ap,
+                            const akr_rect *tiles, int32_t n_tiles, float *radiance, float *weight,
+                            akr_adaptive_info *info);
+/* Device form: overwrites packed buffers like akr_hip_render_device.  The passes are enqueued on
+ * `stream`, and the call waits on the host for each pass's active count. */
+int akr_hip_render_adaptive_device(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_adaptive_params *ap,
+                                   const akr_rect *tiles, int32_t n_tiles, float *d_radiance, float *d_weight,
+                                   void *stream, uint64_t *n_pixels, akr_adaptive_info *info);
+/* The same render one pass at a time, for callers that want the film between passes (previews, a time
+ * budget).  akr_hip_adaptive_begin renders min_spp for every slot (starting the session) and takes the
+ * snapshot; each akr_hip_adaptive_step runs one pass over the active strips and its test.  *more is 1
+ * while a pass remains.  begin followed by steps until *more is 0 is akr_hip_render_adaptive, bit for
+ * bit and in `info`; stopping earlier leaves the film and session of the passes done.  Between steps
+ * akr_hip_render_continue with spp 0 returns the film so far; a continue that draws samples ends the
+ * adaptive run (a later step is refused) but keeps the session. */
+int akr_hip_adaptive_begin(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_adaptive_params *ap,
+                           const akr_rect *tiles, int32_t n_tiles, akr_adaptive_info *info, int32_t *more);
+int akr_hip_adaptive_step(akr_hip_ctx *ctx, akr_adaptive_info *info, int32_t *more);
+/* The last convergence test's values of the session's adaptive render, n_strips = ceil(n_pixels / 64):
+ * each strip's error E and whether it is still active.  A strip that stopped earlier keeps the error
+ * it stopped with.  Fails when the session ran no test. */
+int akr_hip_adaptive_error(akr_hip_ctx *ctx, float *strip_error, uint8_t *strip_active, uint64_t n_strips);
 
 /* Host-only BVH build (no device needed): the same builder akr_hip_build_accel runs, for tools
  * and CPU-side checks.  Arrays are owned by the handle; free with akr_bvh_host_free. */
