@@ -669,7 +669,13 @@ class HipContext:
                 "t_shade", "spec_started", "spec_aborted", "tv_issue", "tv_wait", "tv_comp", "tl_issue", "tl_wait",
                 "tl_comp", "tp_park", "tp_next", "tp_begin", "tp_load", "leaf_phases", "leaf_holders",
                 # option count_lines (k_path): distinct 128-B lines the last such render read, per region
-                "lines_nodes", "lines_leaves", "lines_shading")
+                "lines_nodes", "lines_leaves", "lines_shading",
+                # k_path's pop site and push ("bounded pop"): iterations with a pop, the pop
+                # rounds the wave ran in them, the rounds and the pops summed over lanes; iterations with a
+                # push, those in which a lane had fewer than four free LDS rows, and of these the ones whose
+                # entries all fit in LDS
+                "pop_iters", "pop_rounds", "pop_lane_rounds", "pop_lanes", "push_iters", "push_slow",
+                "push_would_fit")
         out = (C.c_uint64 * len(keys))()
         self._check(self.lib.akr_hip_path_profile(self.h, out, len(keys)))
         return dict(zip(keys, (int(v) for v in out)))

@@ -57,6 +57,11 @@ constexpr int kWhileExit = AKR_WHILE_EXIT;  // traversal phase ends when <= this
 #define AKR_WHILE_EXIT_PATH 16  // k_path: 4.034-4.064 against 4.060-4.078 ms per spp at 12, 20 slower (profiles/r24/path_exit_ab.log)
 #endif
 constexpr int kWhileExitPath = AKR_WHILE_EXIT_PATH;  // the same for k_path alone (the other persistent forms keep kWhileExit)
+// k_path's pop site (options path_pop_rounds / path_pop_keep): pop rounds per iteration at most, and the
+// unserved lanes below which the site stops early.  Swept over {1, 2, 3} x {1, 4, 8, 16} on C3: the whole
+// frame runs 3.90-3.93 ms per spp at 2 / 4 and 3.91-3.92 at 3 / 4 against 4.05-4.09 for the parent and for
+// 255 / 1, which waits for the slowest lane (profiles/r28_pop_sweep.log)
+constexpr int kPathPopRounds = 2, kPathPopKeep = 4;
 #ifndef AKR_WHILE_EXIT_SPEC
 #define AKR_WHILE_EXIT_SPEC AKR_WHILE_EXIT
 #endif
@@ -262,6 +267,11 @@ struct PathProfile {
     unsigned long long tp_park, tp_next, tp_begin;
     unsigned long long tp_load;    // of t_shade: until the hit's shading record is loaded
     unsigned long long leaf_phases, leaf_holders;  // leaf phases with a leaf held, lanes holding one (summed per wave)
+    // k_path's pop site and push ("bounded pop"): traversal iterations in which a lane
+    // popped, the pop rounds the wave ran in them, the rounds the lanes needed and the lanes that popped
+    // (both summed per lane); iterations with a push, those of them in which some lane had sp + 4 >
+    // kStackLds (the general push before the fit test), and of those the ones whose entries all fit in LDS
+    unsigned long long pop_iters, pop_rounds, pop_lane_rounds, pop_lanes, push_iters, push_slow, push_would_fit;
 };
 
 // Persistent path kernel (k_path): the whole sample loop of every pixel of the tile list.
@@ -276,6 +286,8 @@ struct PathArgs {
     int32_t max_depth;
     float ray_clamp;
     uint32_t min_wait;             // a wave processes its waiting lanes once min_wait / 64 of its live lanes wait
+    uint32_t pop_keep, pop_rounds; // k_path's pop site: rounds run while >= pop_keep lanes are unserved, at most
+                                   // pop_rounds of them; the lanes left retry in the next iteration
     PathProfile *prof;             // counting build only
     float4 *contrib;               // k_path_defer: per lane, [18][lanes]: 16 NEE contributions awaiting their
                                    // shadow result (parity * 8 + bounce), then the waiting extension ray

@@ -415,6 +415,10 @@ struct akr_hip_ctx {
     // 64 wait (scaled to the wave's live lanes); 0 (default) = 40 (measured on C3, DESIGN.md §3.8: with
     // the paired order the 8-way share runs 0.944-0.948 ms at 40, 0.972 at 32, 1.007 at 56)
     int path_min_wait = 0;
+    // options "path_pop_rounds" / "path_pop_keep" (k_path, DESIGN.md §3.1 "bounded pop"): an iteration's pop
+    // site runs rounds while at least path_pop_keep lanes are unserved, at most path_pop_rounds of them; the
+    // lanes left retry in the next iteration.  255 / 1 waits for the slowest lane, as stack_pop does.
+    int path_pop_rounds = kPathPopRounds, path_pop_keep = kPathPopKeep;
     int path_grid_pct = 100;  // option "path_grid_pct": persistent path grid as a percentage of the resident maximum
     DBuf<float4> d_trace_rays;
     DBuf<akr_hit> d_trace_hits;
@@ -1255,6 +1259,8 @@ struct akr_hip_ctx {
                                               ? std::min(path_order_share_min_spp, path_order_min_spp)
                                               : path_order_min_spp;
                 pa.min_wait = (uint32_t)(path_min_wait > 0 ? path_min_wait : 40);
+                pa.pop_keep = (uint32_t)path_pop_keep;
+                pa.pop_rounds = (uint32_t)path_pop_rounds;
                 const bool forced = path_spec == 1 || path_defer != 2;
                 // the pilot can rank pixels for every form (path_order 2), or for k_path only (1)
                 const bool pilot = path_order != 0 && !subset && p.spp >= order_min_spp && N >= 2 &&
@@ -1708,6 +1714,12 @@ int akr_hip_set_option(akr_hip_ctx *ctx, const char *key, int64_t value) {
         } else if (k == "path_min_wait") {
             if (value < 0 || value > 64) throw std::runtime_error("path_min_wait must be in [0, 64] (0: per kernel)");
             ctx->path_min_wait = (int)value;
+        } else if (k == "path_pop_rounds") {
+            if (value < 1 || value > 255) throw std::runtime_error("path_pop_rounds must be in [1, 255]");
+            ctx->path_pop_rounds = (int)value;
+        } else if (k == "path_pop_keep") {
+            if (value < 1 || value > 64) throw std::runtime_error("path_pop_keep must be in [1, 64]");
+            ctx->path_pop_keep = (int)value;
         } else if (k == "pixel_probe") {
             ctx->probe = value != 0;
             ctx->probe_clock = value == 2;
@@ -2817,7 +2829,10 @@ int akr_hip_path_profile(akr_hip_ctx *ctx, uint64_t *out, int32_t n) {
         uint64_t v[] = {q.waves, q.outer, q.procs, q.trav_iters, q.t_proc, q.t_trav, q.t_leaf, q.t_total, q.t_max,
                         q.lanes_proc, q.t_shade, q.spec_started, q.spec_aborted, q.tv_issue, q.tv_wait,
                         q.tv_comp, q.tl_issue, q.tl_wait, q.tl_comp, q.tp_park, q.tp_next, q.tp_begin, q.tp_load,
-                        q.leaf_phases, q.leaf_holders, 0, 0, 0};
+                        q.leaf_phases, q.leaf_holders, 0, 0, 0,
+                        // out[28..34]: k_path's pop site and push (PathProfile)
+                        q.pop_iters, q.pop_rounds, q.pop_lane_rounds, q.pop_lanes, q.push_iters, q.push_slow,
+                        q.push_would_fit};
         // out[25..27]: distinct 128-B lines of the wide nodes, the leaf blob and the shading records the
         // last render with count_lines read (k_path)
         if (n > 25 && ctx->count_lines && ctx->d_lines.p && ctx->lines_span[3]) {

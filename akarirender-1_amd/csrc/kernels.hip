@@ -147,8 +147,13 @@ __device__ __forceinline__ void issue_together(const float4 &a, const float4 &b,
                  "v"(f.z));
 }
 
+// A lane of k_path whose pop is still owed ("bounded pop"): its stack pointer already
+// stands below the entries it culled, and it pops on at the next iteration's pop site.  It carries the
+// leaf bit, so it is no internal node, and it is neither a leaf nor AKR_CHILD_EMPTY (a leaf reference
+// is a float4 offset into the leaf blob, far below it).
+#define AKR_CHILD_POP 0xFFFFFFFEu
 __device__ __forceinline__ bool is_internal(uint32_t c) { return !(c & AKR_CHILD_LEAF); }
-__device__ __forceinline__ bool is_leaf(uint32_t c) { return (c & AKR_CHILD_LEAF) && c != AKR_CHILD_EMPTY; }
+__device__ __forceinline__ bool is_leaf(uint32_t c) { return (c & AKR_CHILD_LEAF) && c < AKR_CHILD_POP; }
 
 // Traversal stack pointers carry their address space in the type (LDS = 3, global = 1), so the
 // compiler cannot merge the LDS push/pop with the overflow one of the other branch into a single
@@ -241,11 +246,17 @@ __device__ __forceinline__ float ubyte(uint32_t w, int k) {  // v_cvt_f32_ubyte{
 // slots at later positions), so the earliest is popped first.
 // NOPOP: when no slot is entered, return true instead of popping, so the caller pops at one site
 // for this case and for a postponed leaf
-template <bool ANY, bool NOPOP = false>
+// FIT (k_path): the straight-line push is taken whenever every lane's entries fit in LDS (sp + pushes
+// <= kStackLds), not only while every lane has four free rows.  A slot that is not pushed then writes
+// `dead`, a scratch word of the lane's outside the stack, instead of row sp + 3 (which is row kStackLds
+// or above, past the stack, once sp >= kStackLds - 3).  `info` (counting build): bit 0 the lane pushes
+// or continues, bit 1 sp + 4 > kStackLds, bit 2 sp + pushes > kStackLds.
+template <bool ANY, bool NOPOP = false, bool FIT = false>
 __device__ __forceinline__ bool wide_order_push(uint32_t order_lo, uint32_t order_hi, uint32_t dpos, const float (&t)[4],
                                                 const bool (&hit)[4], const uint32_t (&ref)[4], uint32_t &cur, float lim,
                                                 lds_u64 *s_stack, glb_u64 *ovf, uint32_t ovf_threads, uint32_t tid,
-                                                uint32_t gtid, int &sp) {
+                                                uint32_t gtid, int &sp, lds_u64 *dead = nullptr,
+                                                uint32_t *info = nullptr) {
     const uint32_t perm = ((dpos & 4u) ? order_hi : order_lo) >> ((dpos & 3u) << 3);
     const uint32_t pos[4] = {perm & 3u, (perm >> 2) & 3u, (perm >> 4) & 3u, (perm >> 6) & 3u};
     uint32_t pm = 0;  // entered slots, by position
@@ -257,14 +268,25 @@ __device__ __forceinline__ bool wide_order_push(uint32_t order_lo, uint32_t orde
         return false;
     }
     const uint32_t rest = pm & (pm - 1u);  // entered slots after the first: pushed
-    if (__ballot(sp + 4 > kStackLds) == 0) {  // wave-uniform: no exec-mask split in the common case
+    if (info)
+        *info = 1u | (sp + 4 > kStackLds ? 2u : 0u) | (sp + (int)__popc(rest) > kStackLds ? 4u : 0u);
+    // wave-uniform: no exec-mask split in the common case
+    const bool all_lds = FIT ? __ballot(sp + (int)__popc(rest) > kStackLds) == 0 : __ballot(sp + 4 > kStackLds) == 0;
+    if (all_lds) {
         // all in LDS: four unconditional writes, no exec-mask branches; a slot that is not pushed
         // writes entry sp + 3, which lies above the new top (sp grows by at most 3) and is dead
+        // (FIT: the lane's scratch word)
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const bool push = (rest >> pos[k]) & 1u;
-            const int e = sp + (push ? (int)__popc(rest >> (pos[k] + 1u)) : 3);
-            lds_put(s_stack, e, tid, (unsigned long long)ref[k] | ((unsigned long long)__float_as_uint(t[k]) << 32));
+            const unsigned long long v = (unsigned long long)ref[k] | ((unsigned long long)__float_as_uint(t[k]) << 32);
+            if constexpr (FIT) {
+                lds_u64 *p = push ? s_stack + (sp + (int)__popc(rest >> (pos[k] + 1u))) * kTraceBlock + tid : dead;
+                *p = v;
+            } else {
+                const int e = sp + (push ? (int)__popc(rest >> (pos[k] + 1u)) : 3);
+                lds_put(s_stack, e, tid, v);
+            }
         }
     } else {
 #pragma unroll
@@ -351,11 +373,12 @@ __device__ __forceinline__ WideNode wide_load(const float4 *wn, uint32_t cur) {
     return nd;
 }
 
-template <bool ANY, bool NOPOP = false>
+template <bool ANY, bool NOPOP = false, bool FIT = false>
 __device__ __forceinline__ int visit_wide_lean_node(const WideNode &nd, uint32_t &cur, V3 o, uint32_t dpos, V3 invd,
                                                     float tmin, float tmaxp, float best, lds_u64 *s_stack, glb_u64 *ovf,
                                                     uint32_t ovf_threads, uint32_t tid, uint32_t gtid, int &sp,
-                                                    bool *need_pop = nullptr) {
+                                                    bool *need_pop = nullptr, lds_u64 *dead = nullptr,
+                                                    uint32_t *push_info = nullptr) {
     const float4 h = nd.h;
     const uint4 c = nd.c, qa = nd.qa, qb = nd.qb;
     const uint32_t meta = __float_as_uint(h.w);
@@ -390,8 +413,8 @@ __device__ __forceinline__ int visit_wide_lean_node(const WideNode &nd, uint32_t
     }
     const int tested = (c.x != AKR_CHILD_EMPTY) + (c.y != AKR_CHILD_EMPTY) + (c.z != AKR_CHILD_EMPTY) +
                        (c.w != AKR_CHILD_EMPTY);
-    const bool np = wide_order_push<ANY, NOPOP>(qb.z, qb.w, dpos, t, hit, ref, cur, ANY ? tmaxp : best, s_stack, ovf,
-                                                ovf_threads, tid, gtid, sp);
+    const bool np = wide_order_push<ANY, NOPOP, FIT>(qb.z, qb.w, dpos, t, hit, ref, cur, ANY ? tmaxp : best, s_stack, ovf,
+                                                     ovf_threads, tid, gtid, sp, dead, push_info);
     if (NOPOP) *need_pop = np;
     return tested;
 }
@@ -1281,6 +1304,9 @@ struct PathCount {
     unsigned long long tv_issue = 0, tv_wait = 0, tv_comp = 0, tl_issue = 0, tl_wait = 0, tl_comp = 0;
     // leaf phases entered with at least one lane holding a leaf, and those lanes summed
     unsigned long long lphases = 0, lholders = 0;
+    // k_path's pop site and push (PathProfile): wave-uniform tallies, and the per-lane pop rounds and pops
+    unsigned long long pop_iters = 0, pop_rounds = 0, push_iters = 0, push_slow = 0, push_would_fit = 0;
+    unsigned long long pop_lane_rounds = 0, pop_lanes = 0;
     bool deep_now = false;
     // option count_lines (k_path): the bitmap of 128-B lines read, wide nodes in bits [0, span[1]), the
     // leaf blob in [span[1], span[2]) (distinct lines per sample pass against the
@@ -1303,11 +1329,57 @@ __device__ __forceinline__ void mark_lines(uint32_t *map, uint32_t lo, uint32_t 
     }
 }
 
+// k_path's pop site ("bounded pop").  stack_pop's loop holds the wave until its slowest
+// lane has found an entry that `best` does not cull.  Here a round serves every popping lane at once
+// without an exec-mask split (a lane with nothing to pop reads a row it ignores and keeps its state), rounds run
+// while at least `keep` lanes are unserved and at most `max_rounds` of them, and a lane still unserved
+// then keeps its lowered stack pointer, takes AKR_CHILD_POP and pops on at the next iteration's site.
+// It pops the same entries in the same order against a best that can only have shrunk meanwhile.
+// OVF: some popping lane's stack reaches past the LDS part.
+template <bool COUNT, bool OVF>
+__device__ __forceinline__ void pop_bounded(bool need_pop, PathRay &r, const lds_u64 *s_stack, const glb_u64 *ovf,
+                                            uint32_t ovf_threads, uint32_t tid, uint32_t gtid, uint32_t keep,
+                                            uint32_t max_rounds, PathCount &c) {
+    bool unserved = need_pop;
+    uint32_t got = AKR_CHILD_POP;
+    int sp = r.sp;
+    uint32_t rounds = 0;
+    while (true) {
+        const bool has = unserved & (sp > 0);
+        unsigned long long e;
+        if constexpr (!OVF) {
+            // every lane reads, a lane that does not pop a row of its own that it ignores (a popping lane
+            // has sp <= kStackLds by the caller's ballot): selects below, no branch around the read
+            e = lds_get(s_stack, min(max(sp, 1), kStackLds) - 1, tid);
+        } else {
+            e = 0;
+            if (has) {
+                if (sp - 1 < kStackLds) e = lds_get(s_stack, sp - 1, tid);
+                else e = ovf[(size_t)(sp - 1 - kStackLds) * ovf_threads + gtid];
+            }
+        }
+        const bool ok = !(__uint_as_float((uint32_t)(e >> 32)) > r.best);
+        const uint32_t got_entry = ok ? (uint32_t)e : got, got_none = unserved ? AKR_CHILD_EMPTY : got;
+        got = has ? got_entry : got_none;
+        sp -= has ? 1 : 0;
+        if (COUNT) c.pop_lane_rounds += has ? 1 : 0;
+        unserved = has & !ok;
+        rounds++;
+        if ((uint32_t)__popcll(__ballot(unserved)) < keep || rounds >= max_rounds) break;
+    }
+    if (COUNT) c.pop_rounds += rounds;
+    r.sp = sp;
+    if (need_pop) r.cur = got;
+}
+
 // B. k_trace's traversal phase over every busy lane's ray (all rays here are lean)
-template <bool COUNT, int EXIT = kWhileExit>  // EXIT: the phase ends when <= EXIT lanes still search
+// BOUND (k_path): the pop site runs pop_bounded and the push is wide_order_push's FIT form
+template <bool COUNT, int EXIT = kWhileExit, bool BOUND = false>  // EXIT: the phase ends when <= EXIT lanes still search
 __device__ __forceinline__ void path_traverse(bool busy, int kind, PathRay &r, const float4 *wn, lds_u64 *s_stack,
                                               glb_u64 *ovf, uint32_t ovf_threads, uint32_t tid, uint32_t gtid,
-                                              PathCount &c) {
+                                              PathCount &c, uint32_t pop_keep = 1, uint32_t pop_rounds = 255,
+                                              lds_u64 *dead = nullptr) {
+    constexpr bool FIT = BOUND;  // (tools/experiments/push_nofit.patch: the bounded pop alone)
     while (true) {
         [[maybe_unused]] unsigned long long tc = 0;
         bool need_pop = false;  // the visit entered no slot: pop below
@@ -1326,20 +1398,29 @@ __device__ __forceinline__ void path_traverse(bool busy, int kind, PathRay &r, c
             tc = wall_clock64();
             c.tv_issue += tb - ta;
             c.tv_wait += tc - tb;
+            uint32_t pinfo = 0;
             if (vis) {
                 const uint32_t node = r.cur;  // the visit moves r.cur on
-                const int nt = visit_wide_lean_node<false, true>(nd, r.cur, r.o, r.dpos, r.invd, r.tmin, r.tmaxp, r.best,
-                                                                 s_stack, ovf, ovf_threads, tid, gtid, r.sp, &need_pop);
+                const int nt = visit_wide_lean_node<false, true, FIT>(nd, r.cur, r.o, r.dpos, r.invd, r.tmin, r.tmaxp,
+                                                                      r.best, s_stack, ovf, ovf_threads, tid, gtid, r.sp,
+                                                                      &need_pop, dead, &pinfo);
                 c.box[kind] += nt;
                 c.visit[kind]++;
                 c.deep_now = c.deep_now || r.sp > kStackLds;
                 if (c.lines)
                     mark_lines(c.lines, 0u, c.span[1], wn, reinterpret_cast<const char *>(wn) + ((size_t)node << 6), 64u);
             }
+            if (__ballot(pinfo & 1u) != 0) {
+                c.push_iters++;
+                if (__ballot(pinfo & 2u) != 0) {
+                    c.push_slow++;
+                    c.push_would_fit += __ballot(pinfo & 4u) == 0 ? 1 : 0;
+                }
+            }
         } else if (busy && is_internal(r.cur)) {
             const WideNode nd = wide_load(wn, r.cur);
-            visit_wide_lean_node<false, true>(nd, r.cur, r.o, r.dpos, r.invd, r.tmin, r.tmaxp, r.best, s_stack, ovf,
-                                              ovf_threads, tid, gtid, r.sp, &need_pop);
+            visit_wide_lean_node<false, true, FIT>(nd, r.cur, r.o, r.dpos, r.invd, r.tmin, r.tmaxp, r.best, s_stack, ovf,
+                                                   ovf_threads, tid, gtid, r.sp, &need_pop, dead);
         }
         // One pop site per iteration, for a visit that entered no slot and for a leaf to postpone (a
         // popped leaf is postponed in the next iteration: every ray visits the same nodes and leaves
@@ -1350,7 +1431,25 @@ __device__ __forceinline__ void path_traverse(bool busy, int kind, PathRay &r, c
             r.leaf = r.cur;  // postpone the leaf and keep descending
             need_pop = true;
         }
-        if (need_pop) r.cur = stack_pop(s_stack, ovf, ovf_threads, tid, gtid, r.sp, r.best);
+        if constexpr (BOUND) {
+            // a lane whose pop was cut short retries here; until then it counts as searching below, is
+            // no leaf holder through r.cur, and cannot finish (r.cur != AKR_CHILD_EMPTY)
+            need_pop = need_pop || (busy && r.cur == AKR_CHILD_POP);
+            const unsigned long long want = __ballot(need_pop);
+            if (want != 0) {
+                if (COUNT) {
+                    c.pop_iters++;
+                    c.pop_lanes += need_pop ? 1 : 0;
+                }
+                // wave-uniform, as stack_pop's: the overflow form stays out of the common iteration
+                if (__builtin_expect(__ballot(need_pop && r.sp > kStackLds) == 0, 1))
+                    pop_bounded<COUNT, false>(need_pop, r, s_stack, ovf, ovf_threads, tid, gtid, pop_keep, pop_rounds, c);
+                else
+                    pop_bounded<COUNT, true>(need_pop, r, s_stack, ovf, ovf_threads, tid, gtid, pop_keep, pop_rounds, c);
+            }
+        } else {
+            if (need_pop) r.cur = stack_pop(s_stack, ovf, ovf_threads, tid, gtid, r.sp, r.best);
+        }
         const unsigned long long searching = __ballot(busy && r.leaf == AKR_CHILD_EMPTY && r.cur != AKR_CHILD_EMPTY);
         if constexpr (COUNT) {
             const bool stop = (uint32_t)__popcll(searching) <= (uint32_t)EXIT &&
@@ -1620,6 +1719,16 @@ __device__ __forceinline__ void path_count_flush(const PathArgs &pa, PathCount &
         atomicAdd(&q.tl_comp, c.tl_comp);
         atomicAdd(&q.leaf_phases, c.lphases);
         atomicAdd(&q.leaf_holders, c.lholders);
+        atomicAdd(&q.pop_iters, c.pop_iters);
+        atomicAdd(&q.pop_rounds, c.pop_rounds);
+        atomicAdd(&q.push_iters, c.push_iters);
+        atomicAdd(&q.push_slow, c.push_slow);
+        atomicAdd(&q.push_would_fit, c.push_would_fit);
+    }
+    const unsigned long long plr = wave_sum(c.pop_lane_rounds), pln = wave_sum(c.pop_lanes);
+    if (__lane_id() == 0 && pa.prof) {
+        atomicAdd(&pa.prof->pop_lane_rounds, plr);
+        atomicAdd(&pa.prof->pop_lanes, pln);
     }
     const int slot_of[2] = {TRACE_CLOSEST, TRACE_SHADOW};
     for (int m = 0; m < 2; m++) {
@@ -1677,6 +1786,11 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
     const int nb = pa.max_depth == 0 ? 1 : pa.max_depth;  // the trace at depth == max_depth is skipped (§3.3)
     const bool ff = a.any_far_first != 0;
     const auto tab = PathTab<TAB>::make(pa.sc, s_tab);  // one workgroup barrier when TAB
+    // The push's scratch word (wide_order_push, FIT): the park area is dead between path_unpark and the
+    // next path_park, and a wave parks and reads only its own 64 columns.  Those columns of park row 0
+    // are 256 B: viewed as u64, 32 words, one per pair of neighbouring lanes (both write what nobody reads).
+    static_assert(kParkSlots >= 1 && kTraceBlock % 64 == 0, "the push's scratch words lie in a wave's park row 0");
+    lds_u64 *dead = (lds_u64 *)&s_park[0][0] + (tid >> 1);
     PathCount c;
     if (COUNT) {
         c.lines = pa.lines;
@@ -1861,7 +1975,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
         if (!__any(busy)) continue;
         // ---- B. traversal phase, C. leaf phase (k_trace's, shared with k_path_defer)
         const int kd = any ? 1 : 0;
-        path_traverse<COUNT, kWhileExitPath>(busy, kd, r, a.wide_nodes, s_stack, stack_ovf, a.ovf_threads, tid, gtid, c);
+        path_traverse<COUNT, kWhileExitPath, true>(busy, kd, r, a.wide_nodes, s_stack, stack_ovf, a.ovf_threads, tid, gtid,
+                                                   c, pa.pop_keep, pa.pop_rounds, dead);
         if (COUNT) {
             const unsigned long long t = wall_clock64();
             p_tt += t - p_t;

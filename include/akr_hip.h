@@ -219,6 +219,8 @@ const char *akr_hip_last_error(const akr_hip_ctx *ctx);
  * overrides "path_spec_pixels", "path_defer_pixels", "path_defer_min_tris"; k_path_spec's "path_spec_depth",
  * "path_spec_fetch", "path_spec_fetch_pixels";
  * "path_tab", "path_mix", "path_min_wait", "path_grid_pct", "path_prio";
+ * k_path's pop site: "path_pop_rounds" (1..255) and "path_pop_keep" (1..64): pop rounds run while at least
+ * path_pop_keep lanes are unserved, at most path_pop_rounds per iteration (255 / 1: until the slowest lane);
  * the cost order: "path_order", "path_order_min_spp", "path_order_share_pixels", "path_order_share_min_spp",
  * "path_order_shift", "path_order_pair", "path_order_classes", "path_order_cap", "path_order_sub",
  * "path_order_pilot_spp", "wave_order" (the wavefront's camera rays in cost order).
@@ -451,7 +453,10 @@ int akr_hip_trace_counts(akr_hip_ctx *ctx, akr_trace_counts *out);
  * unpark with the new rays' start, and the shading's wait for the hit's record (out[19..22]),
  * then the leaf phases entered with a leaf held and the lanes holding one, summed (out[23..24]), then
  * the distinct 128-B lines of the wide nodes, the leaf blob and the shading records that the last
- * k_path render with "count_lines" read (out[25..27]).
+ * k_path render with "count_lines" read (out[25..27]), then k_path's pop site and push (out[28..34]):
+ * iterations in which a lane popped, the pop rounds the wave ran in them, the rounds and the pops summed
+ * over lanes, iterations with a push, those in which some lane had fewer than four free LDS stack rows,
+ * and of these the ones whose entries all fitted in LDS ("bounded pop").
  * Not part of the reference interface. */
 int akr_hip_path_profile(akr_hip_ctx *ctx, uint64_t *out, int32_t n);
 int akr_hip_reset_stats(akr_hip_ctx *ctx);
