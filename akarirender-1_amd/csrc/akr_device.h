@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/akr_hip.h"
 #include "../../include/akr_bvh_format.h"
+#include "akr_path_forms.h"  // PATH_* kernel forms and FETCH_* fetch orders, shared with the HIP-free path_plan.h
 
 // Device code sees the scene record's pointers as global memory (address space 1), so loads through
 // them are global_load even inside an out-of-line function, where the compiler cannot infer it
@@ -57,11 +58,6 @@ constexpr int kWhileExit = AKR_WHILE_EXIT;  // traversal phase ends when <= this
 #define AKR_WHILE_EXIT_PATH 16  // k_path: 4.034-4.064 against 4.060-4.078 ms per spp at 12, 20 slower (profiles/r24/path_exit_ab.log)
 #endif
 constexpr int kWhileExitPath = AKR_WHILE_EXIT_PATH;  // the same for k_path alone (the other persistent forms keep kWhileExit)
-// k_path's pop site (options path_pop_rounds / path_pop_keep): pop rounds per iteration at most, and the
-// unserved lanes below which the site stops early.  Swept over {1, 2, 3} x {1, 4, 8, 16} on C3: the whole
-// frame runs 3.90-3.93 ms per spp at 2 / 4 and 3.91-3.92 at 3 / 4 against 4.05-4.09 for the parent and for
-// 255 / 1, which waits for the slowest lane (profiles/r28_pop_sweep.log)
-constexpr int kPathPopRounds = 2, kPathPopKeep = 4;
 #ifndef AKR_WHILE_EXIT_SPEC
 #define AKR_WHILE_EXIT_SPEC AKR_WHILE_EXIT
 #endif
@@ -293,7 +289,7 @@ struct PathArgs {
                                    // shadow result (parity * 8 + bounce), then the waiting extension ray
     uint32_t mix;                  // k_path_defer: scrambled pixel order within each XCD shard
     const uint32_t *order;         // optional: fetch index -> slot (cost-ordered fetch)
-    uint32_t order_mode;           // with `order`: FETCH_LINEAR (costliest first) or FETCH_PAIR (kernels.hip)
+    uint32_t order_mode;           // with `order`: a FETCH_* mode: FETCH_LINEAR is costliest first (fetch_pixels, kernels.hip)
     uint32_t prio;                 // 0, or: waves fetching in the first prio/256 of a shard raise their priority
     uint4 *probe;                  // optional, per slot (akr_pixel_probe): final sampler state; the counting
                                    // build adds the pixel's closest-hit and shadow rays

@@ -22,6 +22,8 @@
 #include "akr_device.h"
 #include "bvh_build.h"
 #include "kernels.h"
+#include "options.h"
+#include "path_plan.h"
 
 using namespace akr;
 
@@ -153,22 +155,18 @@ struct akr_hip_ctx {
     int n_cu = 256;
     hipStream_t stream = nullptr;
     std::string err;
+    Options opt;  // every knob akr_hip_set_option sets (options.h)
     // Every trace / render of a context is ordered after the previous one, whatever streams the
     // caller passes: they share the refill counters, the overflow stacks and the queues.
     hipEvent_t ev_done = nullptr;
     bool done_recorded = false;
-    // In-band check that every slot of a render's film holds exactly spp samples (option "verify",
-    // default on): device counter + mapped host word
-    bool verify = true;
+    // the in-band film check (option "verify"): device counter + mapped host word
     DBuf<uint32_t> d_bad;
     uint32_t *h_check = nullptr, *d_check_host = nullptr;
     // Fault word (mapped, coherent host memory): a persistent kernel's hang guard sets it
     // (k_path_defer).  Checked after every render on the host, whatever "verify" says.
     uint32_t *h_fault = nullptr, *d_fault_host = nullptr;
     // Test-only per-slot fingerprint of the last render (option "pixel_probe", akr_pixel_probe)
-    bool probe = false;
-    bool fault_test = false;  // option "fault_test": k_path_defer raises the fault word once (tests)
-    bool probe_clock = false; // option "pixel_probe" 2: completion times in the probe (counting build, diagnostic)
     DBuf<uint4> d_probe;
     uint64_t probe_n = 0;
     bool probe_ok = false;
@@ -296,51 +294,7 @@ struct akr_hip_ctx {
     uint32_t ovf_threads = 0;
     uint32_t trace_grid[3] = {0, 0, 0};
     uint32_t path_grid[3][2] = {{0, 0}, {0, 0}, {0, 0}};  // resident workgroups of the persistent path kernels [kind][tab]
-    // The render form of a constant-shading scene.  A "tail form"
-    // (k_path_spec, or k_path_defer when path_spec is 0) pays where k_path's launch would end on a few
-    // long pixel chains while most lanes idle: few pixels per resident lane, and many pixels whose
-    // paths end at once (the camera ray leaves the scene), whose lanes then free up early.  Both come
-    // from the render itself: pixels per resident lane from the occupancy query, the share of camera
-    // rays that miss from the cost-ordering pilot (which marks them).  A render without a pilot
-    // (below the order's spp floor, or path_order 0) runs k_path.
-    // option "path_defer": 1 = k_path_defer (max_depth <= 8), 0 = k_path, 2 (default) = the rule above
-    int path_defer = 2;
-    // option "path_spec": k_path_spec (lanes left idle by the drained pixel queue run
-    // later samples of a busy pixel from guessed sampler states; committed in order, bit-exact):
-    // 1 = always, 0 = never (the rule's tail form is then k_path_defer), 2 (default) = the tail form
-    // when path_defer is 2.  Measured on C3 at 1040 spp: 8-way share 0.89 -> 0.83 ms per spp against
-    // k_path_defer, 2-way 2.55 -> 2.48 against k_path, the whole frame 5 % slower (profiles/r19_spec_*.log)
-    int path_spec = 2;
-    // option "path_tail_ppl10": tail forms only at most path_tail_ppl10 / 10 pixels per resident lane
-    // (default 6.0).  1080p C3 on one MI355X: the whole frame has 7.9 pixels per lane (k_path 4.61 ms
-    // against 4.85 for k_path_spec), a 2-way share 4.0 (2.55 against 2.48)
-    int64_t path_tail_ppl10 = 60;
-    // option "path_tail_steps": ... and a cost-ordering pilot whose camera rays take at least this many
-    // traversal steps (wide-node visits + triangle tests) on average: long dependent-fetch chains, where
-    // a lane freed early can run work that overlaps them (DESIGN.md §3.12 gives the measured means of
-    // the soup's and the Cornell box's shares; the box's rays are a few steps long, its shares run k_path)
-    int path_tail_steps = 12;
-    // option "path_cache_mb": a BVH of at most this many MiB on the device (wide nodes + leaf blob) is
-    // taken as cache-resident (half the 256-MiB Infinity Cache: the kernel streams its film and rays
-    // beside it, MI355X_MICROARCH.md §Infinity Cache): its rule form is k_path_defer at every size
-    // (the SBVH of a 100K-triangle soup is 10.7 MiB and of a 1M soup 109.8 MiB: both cache-resident,
-    // k_path_defer 4-20 % faster than k_path there; the 10M soup's 1.5 GB tree takes k_path_spec on
-    // rank shares)
-    int64_t path_cache_mb = 128;
-    // explicit overrides of the rule's size test (0, default: pixels per lane): a tail form for renders
-    // of at most this many pixels (options "path_spec_pixels", "path_defer_pixels"); option
-    // "path_defer_min_tris" (0, default: no test) keeps scenes below it on k_path
-    int64_t path_spec_pixels = 0;
-    int64_t path_defer_pixels = 0;
-    int64_t path_defer_min_tris = 0;
-    int path_spec_fetch = 3;   // option "path_spec_fetch": k_path_spec's ordered fetch, FETCH_STRIDE (3); -1 = the path_order_pair rule
-    // ... for renders of at most 1.5 pixels per resident lane (the 8-way share) or, when set, at most
-    // path_spec_fetch_pixels pixels; larger ones (2- and 4-way) take the path_order_pair rule: 2.500 /
-    // 1.399 ms against 2.526 / 1.403 strided (profiles/r20_spec_fetch_ab.log)
-    int64_t path_spec_fetch_pixels = 0;
-    int path_spec_depth = 3;   // option "path_spec_depth": samples in flight beyond a pixel's head (1-3, the
-                               // speculation tree's levels; the r19 main line measured 2, 4, 8, 15 alike, 1 slower,
-                               // profiles/r19_spec_depth.log)
+    // the render form rule is plan_path() in path_plan.h; its knobs are in `opt`
     // the last render's form inputs (akr_hip_render_form_inputs): pixels per lane x 1000, the pilot's
     // rays and their summed steps
     int64_t last_ppl1000 = 0, last_pilot_rays = -1, last_pilot_steps = -1;
@@ -350,76 +304,12 @@ struct akr_hip_ctx {
     // device: resolved on the host by resolve_form() when the form or its inputs are queried
     bool form_pending = false, pilot_sum_pending = false;
     int32_t gate_forms[2] = {AKR_FORM_NONE, AKR_FORM_NONE};
-    bool path_mix = true;     // option "path_mix": k_path_defer fetches pixels in scrambled order
-    bool path_tab = true;     // option "path_tab": persistent kernels read the scene tables from an LDS copy
-    // option "path_order": cost-ordered pixel fetch: a pilot camera ray per pixel
-    // ranks the pixels, and each XCD shard hands out its costliest pixels first, so a launch ends on
-    // cheap ones (in k_path_defer it replaces the scrambled fetch).  2 (default) = both persistent
-    // kernels, 1 = k_path only, 0 = off; renders of at least path_order_min_spp samples only (the
-    // pilot costs about one third of a sample pass); classes
-    // of 2^path_order_shift pilot steps.  Measured on C3 at 64 spp: 2- / 4- / 8-way shares 2-5 % faster
-    int path_order = 2;
-    // option "path_order_pair": the cost-ordered fetch of k_path_defer pairs each shard's costliest
-    // pixels with its cheapest inside a wave (lanes done early take the long pixels' shadow rays)
-    // instead of costliest-first: 1 = on, 0 = off, 3 = on for k_path too, 2 (default) = on for renders of at most
-    // 1.5 pixels per resident lane (the 8-way share of a 1080p frame; measured on C3 at 32 spp, DESIGN.md §3.10: 8-way share 1.007 -> 0.946 ms, 4-way share
-    // 1.499 -> 1.548 ms); option "path_prio": waves whose pixels lie in the first path_prio / 256 of
-    // a cost-ordered shard run at raised issue priority (0 = off; measured without effect)
-    int path_order_pair = 2;
-    int path_prio = 0;
-    // (16: at the driver's 20 spp the order makes the whole 1080p C3 frame 1.6 % faster, pilot included:
-    // 4.905 -> 4.826 ms per spp, three alternating runs each, profiles/r18_order_min_spp_ab.log; it was 64
-    // until the leaf phase fetched two triangles with the header)
-    int path_order_min_spp = 16;
-    // renders of at most path_order_share_pixels pixels (a rank's share of a 2-, 4- or 8-way split)
-    // take the order from path_order_share_min_spp samples: the pilot's cost shrinks with the pixel
-    // count and the launch tail it shortens does not (C3 at 20 spp, DESIGN.md §3.10: 2- / 4- / 8-way
-    // shares 1.5 / 4.5 / 3 % faster with the order, the whole frame unchanged)
-    int64_t path_order_share_pixels = 1200000;
-    int path_order_share_min_spp = 16;
-    int path_order_shift = 2;
-    // option "path_order_classes": at most this many cost classes (1..32), the costliest holding every
-    // pixel above; fewer classes keep more of the tile order inside a shard (16 since r20: whole frame
-    // 4.612 against 4.627 ms per spp, 8-way share 0.803 against 0.808, profiles/r20_order_classes_ab.log)
-    int path_order_classes = 16;
-    // option "path_order_cap": a pilot ray stops after this many steps (0: none); its cost class is
-    // then the cap's.  The pilot is a small latency-bound launch whose length is set by its slowest
-    // ray, while the order only needs coarse classes (soup against background).
-    int path_order_cap = 64;
-    // option "path_order_sub": one pilot ray per 2^path_order_sub slots (neighbours in a tile row
-    // share its cost); 0 = a pilot ray per slot
-    int path_order_sub = 0;
-    // option "path_order_pilot_spp": S > 0 ranks slots by the rays their first S samples take in a
-    // counting k_path render (a path pilot; nothing of it reaches the film or the sampler states)
-    // instead of one pilot camera ray's steps (0, default)
-    int path_order_pilot_spp = 0;
-    // option "wave_order": the wavefront's camera rays queued in the cost order (costliest first in
-    // each shard of the closest-hit launch), by the same rule and floors as the persistent kernels
-    bool wave_order = true;
     DBuf<uint4> d_pprobe;  // the path pilot's per-slot probe
     DBuf<uint32_t> d_okey[2], d_oidx[2], d_owork;
     DBuf<uint8_t> d_otmp;
     DBuf<TraceCounters> d_ocnt;
     bool order_warm = false;
     DBuf<float4> d_contrib;   // k_path_defer: per-lane NEE contributions awaiting their shadow result
-    // option "path": 1 = render with k_path, 0 = the wavefront kernels, 2 (default) = k_path when the
-    // render has at most path_auto_pixels pixels (default: any size; measured on C3, DESIGN.md §3.8,
-    // k_path is 5 % faster than the wavefront on a whole 1080p frame and 19-31 % faster on 2-, 4- and
-    // 8-way shares)
-    int path_kernel = 2;
-    int64_t path_auto_pixels = INT64_MAX;
-    bool path_auto_complex = false;  // option "path_auto_complex": auto also takes k_path for complex shading
-    bool serial_shadow = false;  // option "serial_shadow": wavefront shadow traces on the main stream (isolated timing)
-    bool any_far_first = false;  // option "any_far_first": shadow traversal visits far slots first (measured: more visits on C3)
-    // option "path_min_wait": a persistent kernel's wave processes its waiting lanes once this many of
-    // 64 wait (scaled to the wave's live lanes); 0 (default) = 40 (measured on C3, DESIGN.md §3.8: with
-    // the paired order the 8-way share runs 0.944-0.948 ms at 40, 0.972 at 32, 1.007 at 56)
-    int path_min_wait = 0;
-    // options "path_pop_rounds" / "path_pop_keep" (k_path, DESIGN.md §3.1 "bounded pop"): an iteration's pop
-    // site runs rounds while at least path_pop_keep lanes are unserved, at most path_pop_rounds of them; the
-    // lanes left retry in the next iteration.  255 / 1 waits for the slowest lane, as stack_pop does.
-    int path_pop_rounds = kPathPopRounds, path_pop_keep = kPathPopKeep;
-    int path_grid_pct = 100;  // option "path_grid_pct": persistent path grid as a percentage of the resident maximum
     DBuf<float4> d_trace_rays;
     DBuf<akr_hit> d_trace_hits;
     // akr_hip_render_node on the lead context: the frame and the staging of other contexts' films
@@ -429,31 +319,14 @@ struct akr_hip_ctx {
     DBuf<uint32_t> d_gorder;                               // merge orders of overlapping tiles
     hipEvent_t ev_gather = nullptr;  // this context's push to the lead device is done
 
-    // instrumentation
-    bool stats = false, count = false;
-    bool stats_closest_only = false;  // time trace_closest only (HIP events on every launch cost ~7 % at small ranks)
-    bool exact_cull = false;  // true: the reference intersectAABB (no behind-origin cull)
-    int rays_per_lane = 1;    // trace grid sizing: at least this many queued rays per lane
-    // persistent shadow-trace grid as a percentage of the resident maximum: the shadow trace runs beside
-    // the next closest-hit trace, and 75 % leaves it room (wavefront 5.368 / 5.353 ms per spp against
-    // 5.400 / 5.389 at 100 %, 5.395 / 5.380 at 50 %; profiles/r20_shadow_grid_ab.log)
-    int shadow_grid_pct = 75;
-    bool wide = true;         // 4-wide quantized traversal (false: BVH2 kernel only, for A/B)
-    bool lean = true;         // fused per-node slot-test arithmetic (kernels.hip visit_wide_lean; false: A/B)
+    // instrumentation (its options: options.h)
     int wide_collapse = AKR_COLLAPSE_SAH;  // akr_build_params::wide_collapse of the last build
-    // option "leaf_align" (taken by the next build or import): each leaf record of the device blob
-    // starts on a multiple of this many 16-B words (1 = packed; 8 = a 128-B line, so a leaf of at
-    // most two triangles is one fabric request and the leaf phase's eight-load batch never straddles
-    // two lines, tools/fetch_calib: a straddling 128-B gather costs 1.4 requests per line)
-    int leaf_align = 1;
-    bool ray_steps = false;   // diagnostic: standalone traces record per-ray iterations (counted kernel)
     DBuf<uint32_t> d_steps;
     uint64_t n_steps = 0;
     DBuf<TraceCounters> d_counters;
     DBuf<PathProfile> d_pprof;  // k_path counting build: per-wave phase profile
-    // option count_lines (counting build, k_path): the bitmap of 128-B lines a render read, and the
-    // bit ranges of its three regions (wide nodes, leaf blob, shading records)
-    bool count_lines = false;
+    // option count_lines: the bitmap of 128-B lines a render read, and the bit ranges of its three
+    // regions (wide nodes, leaf blob, shading records)
     DBuf<uint32_t> d_lines;
     uint32_t lines_span[4] = {0, 0, 0, 0};
     std::vector<hipEvent_t> pool;
@@ -498,7 +371,7 @@ struct akr_hip_ctx {
 
     template <class F>
     void timed(const char *name, hipStream_t st, F &&launch) {
-        if (!stats || (stats_closest_only && std::strcmp(name, "trace_closest") != 0 && std::strcmp(name, "path") != 0)) {
+        if (!opt.stats_on() || (opt.stats_closest_only() && std::strcmp(name, "trace_closest") != 0 && std::strcmp(name, "path") != 0)) {
             launch();
             return;
         }
@@ -728,10 +601,10 @@ struct akr_hip_ctx {
     bool unchecked_render = false;
 
     uint32_t grid_for(int mode, uint64_t n) const {
-        const uint64_t per_block = (uint64_t)kTraceBlock * (uint64_t)rays_per_lane;
+        const uint64_t per_block = (uint64_t)kTraceBlock * (uint64_t)opt.rays_per_lane;
         uint64_t need = (n + per_block - 1) / per_block;
         uint64_t cap = trace_grid[mode];
-        if (mode == TRACE_SHADOW) cap = std::max<uint64_t>(1, cap * (uint64_t)shadow_grid_pct / 100);
+        if (mode == TRACE_SHADOW) cap = std::max<uint64_t>(1, cap * (uint64_t)opt.shadow_grid_pct / 100);
         return (uint32_t)std::min<uint64_t>(need, cap);
     }
 
@@ -771,7 +644,7 @@ struct akr_hip_ctx {
     // One trace launch: the 4-wide kernel (which traces its rare NaN-prone rays inline with the
     // exact BVH2 walk), or the BVH2 kernel when the "wide" option is off.
     void trace_launch(int mode, bool tight, const TraceArgs &t, uint64_t n_max, hipStream_t st) {
-        launch_trace(mode, count, tight, wide, t, grid_for(mode, n_max), st);
+        launch_trace(mode, opt.count, tight, opt.wide, t, grid_for(mode, n_max), st);
     }
 
     TraceArgs trace_args(uint32_t *work) {
@@ -781,8 +654,8 @@ struct akr_hip_ctx {
         t.wide_leaves = reinterpret_cast<const float4 *>(d_wleaves.p);
         t.wide_root = wide_root_dev;
         // the lean slot test's slack is derived for frame origins and steps below 2^40
-        t.lean = lean && bvh4.max_abs <= 0x1p40f ? 1u : 0u;
-        t.any_far_first = any_far_first ? 1u : 0u;
+        t.lean = opt.lean && bvh4.max_abs <= 0x1p40f ? 1u : 0u;
+        t.any_far_first = opt.any_far_first ? 1u : 0u;
         t.tris = d_tris.p;
         t.stack_ovf = d_ovf.p;
         t.ovf_threads = ovf_threads;
@@ -797,7 +670,7 @@ struct akr_hip_ctx {
         if (!accel_built) throw std::runtime_error("acceleration structure not built (call akr_hip_build_accel)");
         commit_scene();
         ensure_trace_grid();
-        if (count || ray_steps) {
+        if (opt.count || opt.ray_steps) {
             if (!d_counters.p) {
                 d_counters.reserve(3);
                 HIPCHK(hipMemset(d_counters.p, 0, 3 * sizeof(TraceCounters)));
@@ -817,14 +690,14 @@ struct akr_hip_ctx {
         t.n = (uint32_t)n;
         t.abi_hits = hits;
         int mode = any ? TRACE_ANY : TRACE_CLOSEST;
-        if (ray_steps) {
+        if (opt.ray_steps) {
             d_steps.reserve(n);
             n_steps = n;
             t.ray_steps = d_steps.p;
             timed(any ? "trace_any" : "trace_closest", st,
-                  [&] { launch_trace(mode, true, !exact_cull, wide, t, grid_for(mode, n), st); });
+                  [&] { launch_trace(mode, true, !opt.exact_cull, opt.wide, t, grid_for(mode, n), st); });
         } else {
-            timed(any ? "trace_any" : "trace_closest", st, [&] { trace_launch(mode, !exact_cull, t, n, st); });
+            timed(any ? "trace_any" : "trace_closest", st, [&] { trace_launch(mode, !opt.exact_cull, t, n, st); });
         }
         HIPCHK(hipGetLastError());
         mark_done(st);
@@ -840,7 +713,7 @@ struct akr_hip_ctx {
         if (d_okey[0].n < N || d_oidx[0].n < N) throw std::runtime_error("pixel order buffers not sized");
         const size_t tb = d_otmp.n;
         HIPCHK(hipMemsetAsync(d_owork.p, 0, kTraceWords * sizeof(uint32_t), ms));
-        const uint32_t sub = (uint32_t)path_order_sub, n_rays = (uint32_t)(((uint64_t)N + (1u << sub) - 1) >> sub);
+        const uint32_t sub = (uint32_t)opt.path_order_sub, n_rays = (uint32_t)(((uint64_t)N + (1u << sub) - 1) >> sub);
         launch_pilot_rays(cam, d_pixel.p, n_rays, sub, d_ray0.p, ms);
         TraceArgs t = trace_args(d_owork.p);
         t.rays = d_ray0.p;
@@ -848,11 +721,11 @@ struct akr_hip_ctx {
         t.hits = d_hit.p;
         t.counters = d_ocnt.p;
         t.ray_steps = d_okey[1].p;
-        t.step_cap = (uint32_t)path_order_cap;
+        t.step_cap = (uint32_t)opt.path_order_cap;
         // the steps-only build: no hits, no tallies (the counting build spilled and ran ~20 % longer)
         launch_trace(TRACE_PILOT, false, true, true, t, grid_for(TRACE_CLOSEST, n_rays), ms);
         if (sum_steps) HIPCHK(hipMemsetAsync(d_steps_sum.p, 0, sizeof(unsigned long long), ms));
-        launch_order_keys(d_okey[1].p, N, (uint32_t)path_order_shift, (uint32_t)(path_order_classes - 1), sub,
+        launch_order_keys(d_okey[1].p, N, (uint32_t)opt.path_order_shift, (uint32_t)(opt.path_order_classes - 1), sub,
                           d_okey[0].p, d_oidx[0].p, ms, sum_steps ? d_steps_sum.p : nullptr);
         sort_pixel_order(d_otmp.p, tb, d_okey[0].p, d_okey[1].p, d_oidx[0].p, d_oidx[1].p, N, ms);
         HIPCHK(hipGetLastError());
@@ -908,8 +781,8 @@ struct akr_hip_ctx {
         probe_render(base, tab, N, S, ms);
         launch_probe_cost(d_pprobe.p, N, d_okey[1].p, ms);
         uint32_t shift = 0;
-        while (((max_rays + 1u) >> shift) > (uint32_t)path_order_classes) shift++;
-        launch_order_keys(d_okey[1].p, N, shift, (uint32_t)(path_order_classes - 1), 0, d_okey[0].p, d_oidx[0].p, ms);
+        while (((max_rays + 1u) >> shift) > (uint32_t)opt.path_order_classes) shift++;
+        launch_order_keys(d_okey[1].p, N, shift, (uint32_t)(opt.path_order_classes - 1), 0, d_okey[0].p, d_oidx[0].p, ms);
         sort_pixel_order(d_otmp.p, d_otmp.n, d_okey[0].p, d_okey[1].p, d_oidx[0].p, d_oidx[1].p, N, ms);
         HIPCHK(hipGetLastError());
     }
@@ -1001,7 +874,7 @@ struct akr_hip_ctx {
     // render_device with the check on returns only after the film is complete.
     // per_slot: the film of a session whose slots hold different counts: every weight against d_count
     void verify_weights(hipStream_t st, uint64_t N, int spp, bool per_slot = false) {
-        if (!verify || N == 0) return;
+        if (!opt.verify || N == 0) return;
         if (per_slot && d_count.n < N) throw std::runtime_error("film check: the per-slot counts are missing");
         if (!h_check) {
             HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_check), sizeof(uint32_t),
@@ -1078,11 +951,7 @@ struct akr_hip_ctx {
             count_range(true, m, st, lo, hi);
             if ((int64_t)hi + spp > kSessionSppCap) throw_cap((int32_t)hi, spp);
         }
-        akr_pt_params p{};
-        p.spp = spp;
-        p.max_depth = s.max_depth;
-        p.ray_clamp = s.ray_clamp;
-        p.flags = s.flags;
+        const akr_pt_params p = session_params(spp);
         if (!s.seeded) {  // no sample drawn yet: the slots left out keep their start state x + y * width
             launch_init_seed(d_pixel.p, (uint32_t)N, cam.width, d_seed.p, st);
             s.seeded = true;
@@ -1123,6 +992,16 @@ struct akr_hip_ctx {
         throw Refused("render session: " + std::to_string(have) + " + " + std::to_string(spp) +
                                  " samples per slot exceed 2^24 (the weight is an f32 count)");
     }
+    // the session's parameters with `spp` more samples
+    akr_pt_params session_params(int32_t spp) const {
+        const Session &s = require_session();
+        akr_pt_params p{};
+        p.spp = spp;
+        p.max_depth = s.max_depth;
+        p.ray_clamp = s.ray_clamp;
+        p.flags = s.flags;
+        return p;
+    }
 
     // host waits for both internal streams (before a DMA read-back of the film)
     void host_join() {
@@ -1156,6 +1035,17 @@ struct akr_hip_ctx {
         return rg;
     }
 
+    // what render()'s prologue hands to render_path() / render_wavefront()
+    struct Pass {
+        akr_pt_params p;
+        uint64_t N, M;           // the session's slots, and the slots this pass fetches
+        const uint32_t *subset;  // the list of those (a masked continue), or nullptr: every slot
+        bool cont, resume;       // resume: the slots' sampler states are the ones the last segment left
+        bool tight;
+        uint4 *probe;            // option "pixel_probe"
+        size_t n_count_words;    // one pass's counter set
+    };
+
     // cont: p.spp more samples for every slot of the session: the slots, their film sums
     // and (when the session is seeded) their sampler states are the ones the last segment left
     // subset (with cont): the pass draws its samples for the n_subset slots listed there only (a masked
@@ -1185,203 +1075,168 @@ struct akr_hip_ctx {
             if (done_recorded) HIPCHK(hipEventSynchronize(ev_done));
             check_fault("the previous render_device call (run without verify; reported by the next render)");
         }
-        hipStream_t ms = main_st;
         uint4 *probe_p = nullptr;  // option "pixel_probe"
-        if (probe) {
+        if (opt.probe()) {
             d_probe.reserve(N);
-            HIPCHK(hipMemsetAsync(d_probe.p, 0, N * sizeof(uint4), ms));
+            HIPCHK(hipMemsetAsync(d_probe.p, 0, N * sizeof(uint4), main_st));
             probe_p = d_probe.p;
             probe_n = N;
             probe_ok = true;
         }
-        const SceneDev sd = scene_dev();
-        const bool tight = !(exact_cull || (p.flags & AKR_PT_EXACT_CULL));
-    // Persistent path kernel: every sample of every pixel in one launch.  It
+        const bool tight = !(opt.exact_cull || (p.flags & AKR_PT_EXACT_CULL));
+        const Pass pass{p, N, M, subset, cont, resume, tight, probe_p, n_count_words};
+        // Persistent path kernel: every sample of every pixel in one launch.  It
         // runs the lean wide traversal only; the reference cull, the BVH2 kernel and a wide view whose
         // frames exceed the lean test's bounds keep the wavefront form.
         // auto: the persistent kernel for scenes whose shading is constant Diffuse / Emissive; Glossy,
         // Mix or image textures diverge inside the traversal waves, and the wavefront's separate shade
         // kernel measured faster there (textured hall 11.5 vs 16.0 ms per 4K spp)
-        const bool use_path = path_kernel == 1 || (path_kernel == 2 && (int64_t)M <= path_auto_pixels &&
-                                                   (simple_shading || path_auto_complex));
-        if (use_path && tight && wide && trace_args(nullptr).lean) {
-            if (p.spp > 0) {
-                HIPCHK(hipMemsetAsync(d_counts.p, 0, kWorkWords * sizeof(uint32_t), ms));
-                PathArgs pa{};
-                pa.t = trace_args(nullptr);
-                pa.sc = sd;
-                pa.cam = cam;
-                pa.pixel = d_pixel.p;
-                pa.film = d_film.p;
-                pa.work = d_counts.p;
-                pa.n_pix = (uint32_t)M;
-                pa.spp = (uint32_t)p.spp;
-                pa.max_depth = p.max_depth;
-                pa.ray_clamp = p.ray_clamp;
-                pa.prof = count ? d_pprof.p : nullptr;
-                if (count && count_lines) {
-                    auto span = [](const void *p, size_t bytes) {
-                        const uint64_t a = (uint64_t)p;
-                        return (uint32_t)(bytes ? ((a + bytes - 1) >> 7) - (a >> 7) + 1 : 0);
-                    };
-                    lines_span[0] = 0;
-                    lines_span[1] = span(d_wnodes.p, d_wnodes.n * sizeof(akr_bvh4_node));
-                    lines_span[2] = lines_span[1] + span(d_wleaves.p, d_wleaves.n * sizeof(float4));
-                    lines_span[3] = lines_span[2] + span(d_shade_tri.p, d_shade_tri.n * sizeof(ShadeTri));
-                    d_lines.reserve(lines_span[3] / 32 + 1);
-                    HIPCHK(hipMemsetAsync(d_lines.p, 0, (lines_span[3] / 32 + 1) * sizeof(uint32_t), ms));
-                    pa.lines = d_lines.p;
-                    for (int r = 0; r < 4; r++) pa.lines_span[r] = lines_span[r];
-                }
-                pa.probe = probe_p;
-                pa.fault = d_fault_host;
-                pa.fault_test = fault_test ? 1u : 0u;
-                pa.probe_clock = probe_clock ? 1u : 0u;
-                pa.spec_depth = (uint32_t)path_spec_depth;
-                pa.state_in = resume ? d_seed.p : nullptr;  // in place: a slot is fetched by one lane per launch
-                pa.state_out = d_seed.p;
-                // the shading's material / light / CDF tables in LDS when they fit
-                const bool tab = path_tab && path_tab_fits(n_mats, n_lights);
-                // pixels per resident lane of k_path (the occupancy query's grid)
-                const uint64_t lanes = std::max<uint64_t>(1, (uint64_t)path_grid[PATH_PLAIN][tab] *
-                                                                 (uint64_t)path_grid_pct / 100) * kTraceBlock;
-                const int64_t ppl1000 = (int64_t)((M * 1000 + lanes / 2) / lanes);
-                last_ppl1000 = ppl1000;
-                last_pilot_rays = last_pilot_steps = -1;
-                form_pending = pilot_sum_pending = false;
-                // the first persistent render of a context runs the pilot once on a few pixels: its
-                // kernels (and rocPRIM's) are loaded then, not inside a later ordered render
-                if (path_order != 0 && !order_warm) {
-                    pixel_order((uint32_t)std::min<uint64_t>(N, 64), ms);
-                    order_warm = true;
-                }
-                const int order_min_spp = (int64_t)N <= path_order_share_pixels
-                                              ? std::min(path_order_share_min_spp, path_order_min_spp)
-                                              : path_order_min_spp;
-                pa.min_wait = (uint32_t)(path_min_wait > 0 ? path_min_wait : 40);
-                pa.pop_keep = (uint32_t)path_pop_keep;
-                pa.pop_rounds = (uint32_t)path_pop_rounds;
-                const bool forced = path_spec == 1 || path_defer != 2;
-                // the pilot can rank pixels for every form (path_order 2), or for k_path only (1)
-                const bool pilot = path_order != 0 && !subset && p.spp >= order_min_spp && N >= 2 &&
-                                   (path_order == 2 || (!forced || (path_spec != 1 && path_defer == 0)));
-                // a continued render ranks by the camera-ray pilot: the path pilot renders into the film
-                const bool path_pilot = pilot && path_order_pilot_spp > 0 && !cont;
-                // the rule: its size and scene tests, then the camera-ray pilot's mean steps
-                const bool size_ok = ppl1000 <= path_tail_ppl10 * 100;
-                const bool tris_ok = path_defer_min_tris == 0 || (int64_t)n_tris() >= path_defer_min_tris;
-                // the BVH's device bytes against the Infinity Cache share: a cache-resident
-                // tree takes k_path_defer at any size, a larger one k_path_spec up to path_tail_ppl10
-                const uint64_t bvh_bytes = bvh_dev_bytes;
-                const bool cache_resident = path_spec != 1 && p.max_depth <= 8 && bvh_bytes <= (uint64_t)path_cache_mb << 20;
-                const bool size_tail = path_spec == 2 ? (path_spec_pixels > 0 ? (int64_t)N <= path_spec_pixels : size_ok)
-                                                      : (path_defer_pixels > 0 ? (int64_t)N <= path_defer_pixels : size_ok);
-                const bool want_steps = !forced && path_order == 2 && pilot && !path_pilot && tris_ok && (cache_resident || size_tail);
-                if (pilot) {
-                    if (path_pilot)
-                        timed("pilot", ms, [&] { pixel_order_path(pa, tab, (uint32_t)N, path_order_pilot_spp, ms); });
-                    else
-                        timed("pilot", ms, [&] { pixel_order((uint32_t)N, ms, want_steps); });
-                    pa.order = d_oidx[1].p;
-                }
-                // The rule's tail test reads the pilot's step sum, which is on the device: no host wait
-                // inside the render.  k_pick_form writes a gate word from the sum, and both
-                // candidate kernels are launched back to back, each exiting at once unless the gate
-                // names it; the form that ran is read back only when akr_hip_render_form asks.
-                const int tail_kind = cache_resident ? PATH_DEFER
-                                                     : (path_spec == 2 ? PATH_SPEC : (p.max_depth <= 8 ? PATH_DEFER : PATH_PLAIN));
-                const bool gated = want_steps && tail_kind != PATH_PLAIN;
-                int kind = PATH_PLAIN;
-                if (path_spec == 1) kind = PATH_SPEC;
-                else if (path_defer == 1 && p.max_depth <= 8) kind = PATH_DEFER;
-                // one candidate's launch arguments and grid
-                auto configure = [&](int k, PathArgs &x) {
-                    const uint64_t resident = (uint64_t)path_grid[k][tab] * (uint64_t)path_grid_pct / 100;
-                    const uint32_t grid = (uint32_t)std::max<uint64_t>(
-                        1, std::min<uint64_t>(resident, (M + kTraceBlock - 1) / kTraceBlock));
-                    if (k == PATH_DEFER) {
-                        d_contrib.reserve((size_t)18 * grid * kTraceBlock);  // 16 NEE slots + the waiting ray
-                        x.contrib = d_contrib.p;
-                        x.mix = path_mix ? 1u : 0u;
-                    }
-                    if (subset) {  // the active list in ascending order (k_path_defer keeps its scramble)
-                        x.order = subset;
-                        x.order_mode = k == PATH_DEFER && path_mix ? 1u : 0u;  // FETCH_SCRAMBLE / FETCH_LINEAR
-                        x.prio = 0u;
-                        return grid;
-                    }
-                    if (x.order && !(k == PATH_PLAIN || path_order == 2)) x.order = nullptr;  // path_order 1
-                    if (x.order) {
-                        const bool small = ppl1000 <= 1500;  // at most 1.5 pixels per resident lane (8-way share)
-                        const bool pair = path_order_pair == 3 ||
-                                          (k != PATH_PLAIN && (path_order_pair == 1 || (path_order_pair == 2 && small)));
-                        x.order_mode = pair ? 2u : 0u;  // FETCH_PAIR / FETCH_LINEAR
-                        // k_path_spec: every wave takes pixels from the whole cost order (FETCH_STRIDE), so
-                        // each has cheap pixels whose lanes turn helpers early (option path_spec_fetch)
-                        if (k == PATH_SPEC && path_spec_fetch >= 0 &&
-                            (path_spec_fetch_pixels > 0 ? (int64_t)N <= path_spec_fetch_pixels : small))
-                            x.order_mode = (uint32_t)path_spec_fetch;
-                        x.prio = (uint32_t)path_prio;
-                    }
-                    return grid;
-                };
-                auto form_of = [](int k) {
-                    return k == PATH_SPEC ? AKR_FORM_PATH_SPEC : (k == PATH_DEFER ? AKR_FORM_PATH_DEFER : AKR_FORM_PATH);
-                };
-                if (want_steps) last_pilot_rays = (int64_t)(((uint64_t)N + (1u << path_order_sub) - 1) >> path_order_sub);
-                if (gated) {
-                    launch_pick_form(d_steps_sum.p, (unsigned long long)path_tail_steps * (uint64_t)last_pilot_rays,
-                                     d_gate.p, ms);
-                    PathArgs p0 = pa, p1 = pa;
-                    const uint32_t g0 = configure(PATH_PLAIN, p0), g1 = configure(tail_kind, p1);
-                    p0.gate = p1.gate = d_gate.p;
-                    p0.gate_want = 0u;
-                    p1.gate_want = 1u;
-                    timed("path", ms, [&] {  // one timed record: the launch that exits at once adds microseconds
-                        launch_path(count, PATH_PLAIN, tab, p0, g0, ms);
-                        launch_path(count, tail_kind, tab, p1, g1, ms);
-                    });
-                    HIPCHK(hipGetLastError());
-                    gate_forms[0] = form_of(PATH_PLAIN);
-                    gate_forms[1] = form_of(tail_kind);
-                    form_pending = true;
-                    last_form = AKR_FORM_NONE;
-                    pa.order = p0.order;
-                } else {
-                    if (want_steps) pilot_sum_pending = true;  // the step sum is read back on request
-                    const uint32_t grid = configure(kind, pa);
-                    timed("path", ms, [&] { launch_path(count, kind, tab, pa, grid, ms); });
-                    HIPCHK(hipGetLastError());
-                    last_form = form_of(kind);
-                }
-                last_ordered = pa.order && !subset ? 1 : 0;
-                // a subset pass wrote the probe of its slots only: the others keep the state they had
-                if (subset && probe_p)
-                    launch_probe_fill(d_seed.p, (uint32_t)N, probe_p, AKR_PROBE_SEED | (count ? AKR_PROBE_RAYS : 0u), ms);
-            }
+        const bool use_path = opt.path_kernel == 1 || (opt.path_kernel == 2 && (int64_t)M <= opt.path_auto_pixels &&
+                                                       (simple_shading || opt.path_auto_complex));
+        if (use_path && tight && opt.wide && trace_args(nullptr).lean) {
+            if (p.spp > 0) render_path(pass);
             last_passes = 1;
-            join_streams(st);
-            return N;
+        } else {
+            render_wavefront(pass);
         }
+        join_streams(st);
+        return N;
+    }
+
+    // the first ordered render of a context runs the pilot once on a few pixels: its kernels (and
+    // rocPRIM's) are loaded then, not inside a later ordered render
+    void warm_order(uint64_t N, hipStream_t ms) {
+        if (order_warm) return;
+        pixel_order((uint32_t)std::min<uint64_t>(N, 64), ms);
+        order_warm = true;
+    }
+
+    // The persistent half of render(): the pilot plan_path() (path_plan.h) asks for, then
+    // the one or two launches it lists
+    void render_path(const Pass &r) {
+        const akr_pt_params &p = r.p;
+        const uint64_t N = r.N;
+        hipStream_t ms = main_st;
+        HIPCHK(hipMemsetAsync(d_counts.p, 0, kWorkWords * sizeof(uint32_t), ms));
+        PathArgs pa{};
+        pa.t = trace_args(nullptr);
+        pa.sc = scene_dev();
+        pa.cam = cam;
+        pa.pixel = d_pixel.p;
+        pa.film = d_film.p;
+        pa.work = d_counts.p;
+        pa.n_pix = (uint32_t)r.M;
+        pa.spp = (uint32_t)p.spp;
+        pa.max_depth = p.max_depth;
+        pa.ray_clamp = p.ray_clamp;
+        pa.prof = opt.count ? d_pprof.p : nullptr;
+        if (opt.count && opt.count_lines) {
+            auto span = [](const void *p, size_t bytes) {
+                const uint64_t a = (uint64_t)p;
+                return (uint32_t)(bytes ? ((a + bytes - 1) >> 7) - (a >> 7) + 1 : 0);
+            };
+            lines_span[0] = 0;
+            lines_span[1] = span(d_wnodes.p, d_wnodes.n * sizeof(akr_bvh4_node));
+            lines_span[2] = lines_span[1] + span(d_wleaves.p, d_wleaves.n * sizeof(float4));
+            lines_span[3] = lines_span[2] + span(d_shade_tri.p, d_shade_tri.n * sizeof(ShadeTri));
+            d_lines.reserve(lines_span[3] / 32 + 1);
+            HIPCHK(hipMemsetAsync(d_lines.p, 0, (lines_span[3] / 32 + 1) * sizeof(uint32_t), ms));
+            pa.lines = d_lines.p;
+            for (int k = 0; k < 4; k++) pa.lines_span[k] = lines_span[k];
+        }
+        pa.probe = r.probe;
+        pa.fault = d_fault_host;
+        pa.fault_test = opt.fault_test ? 1u : 0u;
+        pa.probe_clock = opt.probe_clock() ? 1u : 0u;
+        pa.spec_depth = (uint32_t)opt.path_spec_depth;
+        pa.state_in = r.resume ? d_seed.p : nullptr;  // in place: a slot is fetched by one lane per launch
+        pa.state_out = d_seed.p;
+        pa.min_wait = (uint32_t)(opt.path_min_wait > 0 ? opt.path_min_wait : 40);
+        pa.pop_keep = (uint32_t)opt.path_pop_keep;
+        pa.pop_rounds = (uint32_t)opt.path_pop_rounds;
+        // the shading's material / light / CDF tables in LDS when they fit
+        const bool tab = opt.path_tab && path_tab_fits(n_mats, n_lights);
+        PathPlanIn in;
+        in.N = N;
+        in.M = r.M;
+        in.spp = p.spp;
+        in.max_depth = p.max_depth;
+        in.cont = r.cont;
+        in.subset = r.subset != nullptr;
+        in.n_tris = n_tris();
+        in.bvh_dev_bytes = bvh_dev_bytes;
+        for (int k = 0; k < 3; k++) in.grid[k] = path_grid[k][tab];
+        in.block = kTraceBlock;
+        const PathPlan pl = plan_path(in, opt);
+        last_ppl1000 = pl.ppl1000;
+        last_pilot_rays = pl.pilot_rays;
+        last_pilot_steps = -1;
+        if (opt.path_order != 0) warm_order(N, ms);
+        if (pl.pilot) {
+            if (pl.path_pilot)
+                timed("pilot", ms, [&] { pixel_order_path(pa, tab, (uint32_t)N, opt.path_order_pilot_spp, ms); });
+            else
+                timed("pilot", ms, [&] { pixel_order((uint32_t)N, ms, pl.want_steps); });
+        }
+        // The rule's tail test reads the pilot's step sum, which is on the device: no host wait
+        // inside the render.  k_pick_form writes a gate word from the sum, and both
+        // candidate kernels are launched back to back, each exiting at once unless the gate
+        // names it; the form that ran is read back only when akr_hip_render_form asks.
+        if (pl.gated)
+            launch_pick_form(d_steps_sum.p, (unsigned long long)opt.path_tail_steps * (uint64_t)pl.pilot_rays, d_gate.p, ms);
+        PathArgs args[2] = {pa, pa};
+        for (int k = 0; k < pl.n_launch; k++) {
+            const PathLaunch &l = pl.launch[k];
+            PathArgs &x = args[k];
+            if (l.contrib_lanes) {
+                d_contrib.reserve((size_t)18 * l.contrib_lanes);  // 16 NEE slots + the waiting ray
+                x.contrib = d_contrib.p;
+            }
+            x.mix = l.mix;
+            x.order = l.list == LIST_PILOT ? d_oidx[1].p : (l.list == LIST_SUBSET ? r.subset : nullptr);
+            x.order_mode = l.order_mode;
+            x.prio = l.prio;
+            if (pl.gated) {
+                x.gate = d_gate.p;
+                x.gate_want = (uint32_t)k;
+            }
+        }
+        timed("path", ms, [&] {  // one timed record: a gated launch that exits at once adds microseconds
+            for (int k = 0; k < pl.n_launch; k++) launch_path(opt.count, pl.launch[k].kind, tab, args[k], pl.launch[k].grid, ms);
+        });
+        HIPCHK(hipGetLastError());
+        form_pending = pl.gated;
+        pilot_sum_pending = pl.want_steps && !pl.gated;  // the step sum is read back on request
+        if (pl.gated) std::copy(pl.gate_forms, pl.gate_forms + 2, gate_forms);
+        last_form = pl.last_form;
+        last_ordered = pl.last_ordered;
+        // a subset pass wrote the probe of its slots only: the others keep the state they had
+        if (r.subset && r.probe)
+            launch_probe_fill(d_seed.p, (uint32_t)N, r.probe, AKR_PROBE_SEED | (opt.count ? AKR_PROBE_RAYS : 0u), ms);
+    }
+
+    // The wavefront half of render(): raygen -> {closest-hit -> shade -> shadow}^depth -> splat per sample pass
+    void render_wavefront(const Pass &r) {
+        const akr_pt_params &p = r.p;
+        const uint64_t N = r.N, M = r.M;
+        const uint32_t *subset = r.subset;
+        const bool resume = r.resume, tight = r.tight;
+        uint4 *probe_p = r.probe;
+        const size_t n_count_words = r.n_count_words;
+        const int D = p.max_depth + 2;
+        hipStream_t ms = main_st;
+        const SceneDev sd = scene_dev();
         if (p.spp > 0) last_form = AKR_FORM_WAVEFRONT;
         const int nb = p.max_depth == 0 ? 1 : p.max_depth;  // the trace at depth == max_depth can
                                                              // add nothing: skipped
         int64_t g = 0;  // bounce index over all passes: shadow queues alternate by its parity
         const uint32_t *worder = nullptr;  // the cost order of the camera rays (option wave_order)
-        {
-            const int order_min_spp = (int64_t)N <= path_order_share_pixels
-                                          ? std::min(path_order_share_min_spp, path_order_min_spp)
-                                          : path_order_min_spp;
-            if (wave_order && path_order != 0 && !subset && p.spp >= order_min_spp && N >= 2) {
-                if (!order_warm) {
-                    pixel_order((uint32_t)std::min<uint64_t>(N, 64), ms);
-                    order_warm = true;
-                }
-                timed("pilot", ms, [&] { pixel_order((uint32_t)N, ms); });
-                worder = d_oidx[1].p;
-            }
-            last_ordered = worder ? 1 : 0;
+        if (opt.wave_order && opt.path_order != 0 && !subset && p.spp >= order_min_spp(opt, N) && N >= 2) {
+            warm_order(N, ms);
+            timed("pilot", ms, [&] { pixel_order((uint32_t)N, ms); });
+            worder = d_oidx[1].p;
         }
+        last_ordered = worder ? 1 : 0;
         for (int s = 0; s < p.spp; s++) {
             const int ps = s & 1;
             last_passes++;
@@ -1438,10 +1293,10 @@ struct akr_hip_ctx {
                     ts.shadow_color = d_scolor[sq].p;
                     ts.L = L;
                     // option serial_shadow (measurement): on the main stream, so the launch is timed alone
-                    hipStream_t sst = serial_shadow ? ms : side;
+                    hipStream_t sst = opt.serial_shadow ? ms : side;
                     timed("trace_shadow", sst, [&] { trace_launch(TRACE_SHADOW, tight, ts, M, sst); });
                 }
-                if (serial_shadow) {
+                if (opt.serial_shadow) {
                     HIPCHK(hipEventRecord(ev_shadow[sq], ms));
                     HIPCHK(hipStreamWaitEvent(side, ev_shadow[sq], 0));
                 } else {
@@ -1461,8 +1316,6 @@ struct akr_hip_ctx {
         }
         // the last shade of every pass ran on the main stream and left each slot's sampler state
         if (probe_p && p.spp > 0) launch_probe_seed(d_seed.p, (uint32_t)N, probe_p, ms);
-        join_streams(st);
-        return N;
     }
 
     // cpu::AmbientOcclusion::render (kernel/integrators/cpu/integrator.cpp:40-87) as one wavefront
@@ -1484,7 +1337,7 @@ struct akr_hip_ctx {
         if (!shadow_mode)
             for (int k = 0; k < 2; k++) d_ao_slot[k].reserve(N);
         hipStream_t ms = main_st;
-        const bool tight = !(exact_cull || (p.flags & AKR_PT_EXACT_CULL));
+        const bool tight = !(opt.exact_cull || (p.flags & AKR_PT_EXACT_CULL));
         for (int s = 0; s < p.spp; s++) {
             const int ps = s & 1;
             uint32_t *cnt = d_counts.p + (size_t)ps * n_count_words;
@@ -1601,138 +1454,8 @@ const char *akr_hip_last_error(const akr_hip_ctx *ctx) { return ctx ? ctx->err.c
 
 int akr_hip_set_option(akr_hip_ctx *ctx, const char *key, int64_t value) {
     return guard(ctx, [&] {
-        std::string k = key ? key : "";
-        if (k == "stats") {  // 1: every kernel; 2: the dominant kernel (trace_closest, or path) only
-            ctx->stats = value != 0;
-            ctx->stats_closest_only = value == 2;
-        } else if (k == "exact_cull") {
-            ctx->exact_cull = value != 0;
-        } else if (k == "count_tests") {
-            ctx->count = value != 0;
-        } else if (k == "count_lines") {  // with count_tests: k_path marks the 128-B lines it reads
-            ctx->count_lines = value != 0;
-        } else if (k == "ray_steps") {
-            ctx->ray_steps = value != 0;
-        } else if (k == "wide") {
-            ctx->wide = value != 0;
-        } else if (k == "lean") {
-            ctx->lean = value != 0;
-        } else if (k == "shadow_grid_pct") {
-            if (value < 1 || value > 100) throw std::runtime_error("shadow_grid_pct must be in [1, 100]");
-            ctx->shadow_grid_pct = (int)value;
-        } else if (k == "path") {
-            if (value < 0 || value > 2) throw std::runtime_error("path must be 0 (wavefront), 1 (path kernel) or 2 (auto)");
-            ctx->path_kernel = (int)value;
-        } else if (k == "path_auto_complex") {
-            ctx->path_auto_complex = value != 0;
-        } else if (k == "path_auto_pixels") {
-            if (value < 0) throw std::runtime_error("path_auto_pixels must be >= 0");
-            ctx->path_auto_pixels = value;
-        } else if (k == "serial_shadow") {
-            ctx->serial_shadow = value != 0;
-        } else if (k == "any_far_first") {
-            ctx->any_far_first = value != 0;
-        } else if (k == "path_defer") {
-            if (value < 0 || value > 2) throw std::runtime_error("path_defer must be 0, 1 or 2 (auto)");
-            ctx->path_defer = (int)value;
-        } else if (k == "path_defer_min_tris") {
-            if (value < 0) throw std::runtime_error("path_defer_min_tris must be >= 0");
-            ctx->path_defer_min_tris = value;
-        } else if (k == "path_defer_pixels") {
-            if (value < 0) throw std::runtime_error("path_defer_pixels must be >= 0");
-            ctx->path_defer_pixels = value;
-        } else if (k == "path_order") {
-            if (value < 0 || value > 2) throw std::runtime_error("path_order must be 0, 1 or 2");
-            ctx->path_order = (int)value;
-        } else if (k == "path_order_min_spp") {
-            if (value < 0) throw std::runtime_error("path_order_min_spp must be >= 0");
-            ctx->path_order_min_spp = (int)std::min<int64_t>(value, INT32_MAX);
-        } else if (k == "path_order_share_pixels") {
-            if (value < 0) throw std::runtime_error("path_order_share_pixels must be >= 0");
-            ctx->path_order_share_pixels = value;
-        } else if (k == "path_order_share_min_spp") {
-            if (value < 0) throw std::runtime_error("path_order_share_min_spp must be >= 0");
-            ctx->path_order_share_min_spp = (int)std::min<int64_t>(value, INT32_MAX);
-        } else if (k == "path_order_cap") {
-            if (value < 0 || value > INT32_MAX) throw std::runtime_error("path_order_cap must be in [0, 2^31)");
-            ctx->path_order_cap = (int)value;
-        } else if (k == "path_order_sub") {
-            if (value < 0 || value > 5) throw std::runtime_error("path_order_sub must be in [0, 5]");
-            ctx->path_order_sub = (int)value;
-        } else if (k == "path_order_classes") {
-            if (value < 1 || value > 32) throw std::runtime_error("path_order_classes must be in [1, 32]");
-            ctx->path_order_classes = (int)value;
-        } else if (k == "path_order_shift") {
-            if (value < 0 || value > 31) throw std::runtime_error("path_order_shift must be in [0, 31]");
-            ctx->path_order_shift = (int)value;
-        } else if (k == "path_order_pair") {
-            if (value < 0 || value > 3)
-                throw std::runtime_error("path_order_pair must be 0, 1, 2 (auto) or 3 (both persistent kernels)");
-            ctx->path_order_pair = (int)value;
-        } else if (k == "path_prio") {
-            if (value < 0 || value > 256) throw std::runtime_error("path_prio must be in [0, 256]");
-            ctx->path_prio = (int)value;
-        } else if (k == "path_mix") {
-            ctx->path_mix = value != 0;
-        } else if (k == "path_tab") {
-            ctx->path_tab = value != 0;
-        } else if (k == "path_spec") {
-            if (value < 0 || value > 2) throw std::runtime_error("path_spec must be 0, 1 or 2");
-            ctx->path_spec = (int)value;
-        } else if (k == "wave_order") {
-            ctx->wave_order = value != 0;
-        } else if (k == "path_order_pilot_spp") {
-            if (value < 0 || value > 64) throw std::runtime_error("path_order_pilot_spp must be in [0, 64]");
-            ctx->path_order_pilot_spp = (int)value;
-        } else if (k == "path_spec_depth") {
-            if (value < 1 || value > 3) throw std::runtime_error("path_spec_depth must be in [1, 3]");
-            ctx->path_spec_depth = (int)value;
-        } else if (k == "path_spec_fetch_pixels") {
-            if (value < 0) throw std::runtime_error("path_spec_fetch_pixels must be >= 0");
-            ctx->path_spec_fetch_pixels = value;
-        } else if (k == "path_spec_fetch") {
-            if (value < -1 || value > 3) throw std::runtime_error("path_spec_fetch must be in [-1, 3]");
-            ctx->path_spec_fetch = (int)value;
-        } else if (k == "path_tail_ppl10") {
-            if (value < 0) throw std::runtime_error("path_tail_ppl10 must be >= 0");
-            ctx->path_tail_ppl10 = value;
-        } else if (k == "leaf_align") {
-            if (value != 1 && value != 2 && value != 4 && value != 8) throw std::runtime_error("leaf_align must be 1, 2, 4 or 8");
-            ctx->leaf_align = (int)value;
-        } else if (k == "path_cache_mb") {
-            if (value < 0) throw std::runtime_error("path_cache_mb must be >= 0");
-            ctx->path_cache_mb = value;
-        } else if (k == "path_tail_steps") {
-            if (value < 0 || value > 4096) throw std::runtime_error("path_tail_steps must be in [0, 4096]");
-            ctx->path_tail_steps = (int)value;
-        } else if (k == "path_spec_pixels") {
-            if (value < 0) throw std::runtime_error("path_spec_pixels must be >= 0");
-            ctx->path_spec_pixels = value;
-        } else if (k == "path_grid_pct") {
-            if (value < 1 || value > 100) throw std::runtime_error("path_grid_pct must be in [1, 100]");
-            ctx->path_grid_pct = (int)value;
-        } else if (k == "path_min_wait") {
-            if (value < 0 || value > 64) throw std::runtime_error("path_min_wait must be in [0, 64] (0: per kernel)");
-            ctx->path_min_wait = (int)value;
-        } else if (k == "path_pop_rounds") {
-            if (value < 1 || value > 255) throw std::runtime_error("path_pop_rounds must be in [1, 255]");
-            ctx->path_pop_rounds = (int)value;
-        } else if (k == "path_pop_keep") {
-            if (value < 1 || value > 64) throw std::runtime_error("path_pop_keep must be in [1, 64]");
-            ctx->path_pop_keep = (int)value;
-        } else if (k == "pixel_probe") {
-            ctx->probe = value != 0;
-            ctx->probe_clock = value == 2;
-        } else if (k == "fault_test") {
-            ctx->fault_test = value != 0;
-        } else if (k == "verify") {
-            ctx->verify = value != 0;
-        } else if (k == "rays_per_lane") {
-            if (value < 1 || value > 64) throw std::runtime_error("rays_per_lane must be in [1, 64]");
-            ctx->rays_per_lane = (int)value;
-        } else {
-            throw std::runtime_error("unknown option '" + k + "'");
-        }
+        const std::string why = set_option(ctx->opt, key, value);
+        if (!why.empty()) throw std::runtime_error(why);
     });
 }
 
@@ -1879,7 +1602,7 @@ void finish_accel(akr_hip_ctx *ctx, int n_threads) {
         const auto &leaves = ctx->bvh4.leaves;
         std::vector<uint32_t> leaf_off(leaves.size());
         size_t words = 0;
-        const size_t align = (size_t)std::max(1, ctx->leaf_align);
+        const size_t align = (size_t)std::max(1, ctx->opt.leaf_align);
         for (size_t i = 0; i < leaves.size(); i++) {
             words = (words + align - 1) / align * align;
             if (words >= AKR_CHILD_LEAF) break;
@@ -2061,7 +1784,7 @@ int akr_hip_render_node(akr_hip_ctx *const *ctxs, int32_t n_ctx, const akr_pt_pa
             hipStream_t st = c->stream;
             const uint64_t N = c->render(*params, part[k].data(), (int32_t)part[k].size(), st);
             c->verify_weights(st, N, params->spp);  // joins the render into st and checks it
-            if (!c->verify) {
+            if (!c->opt.verify) {
                 c->join_streams(st);
                 HIPCHK(hipStreamSynchronize(st));
                 c->check_fault();
@@ -2194,14 +1917,14 @@ void merge_film(akr_hip_ctx *ctx, uint64_t N, int spp, float *radiance, float *w
     ctx->verify_weights(st, N, spp, per_slot);
     std::vector<float4> film(N);
     std::vector<uint32_t> counts;
-    if (per_slot && ctx->verify) {
+    if (per_slot && ctx->opt.verify) {
         counts.resize(N);
         HIPCHK(hipMemcpyAsync(counts.data(), ctx->d_count.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipMemcpyAsync(film.data(), ctx->d_film.p, N * sizeof(float4), hipMemcpyDeviceToHost, st));
     ctx->mark_done(st);
     HIPCHK(hipStreamSynchronize(st));
-    if (ctx->verify) {  // the read-back itself: every copied slot holds spp samples
+    if (ctx->opt.verify) {  // the read-back itself: every copied slot holds spp samples
         uint64_t bad = 0;
         for (uint64_t k = 0; k < N; k++) bad += film[k].w != (float)(per_slot ? counts[k] : (uint32_t)spp);
         if (bad) throw std::runtime_error("film read-back: " + std::to_string(bad) + " of " + std::to_string(N) +
@@ -2249,28 +1972,29 @@ int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const a
         ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)N, d_radiance, d_weight, st); });
         HIPCHK(hipGetLastError());
         ctx->verify_weights(st, N, params->spp);
-        ctx->unchecked_render = !ctx->verify;
+        ctx->unchecked_render = !ctx->opt.verify;
         ctx->mark_done(st);
         ctx->open_session(*params, N, params->spp, params->spp > 0);
     });
 }
 
 namespace {
-constexpr int32_t kMaxSessionSpp = akr_hip_ctx::kSessionSppCap;
-
-// The session's parameters with `spp` more samples, checked
+// The session's parameters with `spp` more samples for every slot, checked
 akr_pt_params continue_params(akr_hip_ctx *ctx, int32_t spp) {
     const akr_hip_ctx::Session &s = ctx->require_session();
     if (spp < 0) throw std::runtime_error("spp must be >= 0");
-    if ((int64_t)s.spp_done + spp > kMaxSessionSpp)
-        throw std::runtime_error("render session: " + std::to_string(s.spp_done) + " + " + std::to_string(spp) +
-                                 " samples per slot exceed 2^24 (the weight is an f32 count)");
-    akr_pt_params p{};
-    p.spp = spp;
-    p.max_depth = s.max_depth;
-    p.ray_clamp = s.ray_clamp;
-    p.flags = s.flags;
-    return p;
+    if ((int64_t)s.spp_done + spp > akr_hip_ctx::kSessionSppCap) akr_hip_ctx::throw_cap(s.spp_done, spp);
+    return ctx->session_params(spp);
+}
+
+// After a continue of spp > 0 samples for every slot on `st`: the per-slot counts of a non-uniform
+// session, and the copy `s` of the session that the caller stores once the whole call has succeeded
+void advance_session(akr_hip_ctx *ctx, akr_hip_ctx::Session &s, int32_t spp, hipStream_t st) {
+    if (!s.uniform) launch_count_add(ctx->d_count.p, nullptr, (uint32_t)s.n, (uint32_t)spp, st);
+    s.spp_done += spp;
+    s.spp_min += spp;
+    s.seeded = true;
+    s.ad.on = false;
 }
 }  // namespace
 
@@ -2282,11 +2006,7 @@ int akr_hip_render_continue(akr_hip_ctx *ctx, int32_t spp, float *radiance, floa
         try {
             if (spp > 0) {
                 ctx->render(p, nullptr, 0, ctx->stream, true);
-                if (!s.uniform) launch_count_add(ctx->d_count.p, nullptr, (uint32_t)s.n, (uint32_t)spp, ctx->stream);
-                s.spp_done += spp;
-                s.spp_min += spp;
-                s.seeded = true;
-                s.ad.on = false;
+                advance_session(ctx, s, spp, ctx->stream);
             }
             merge_film(ctx, s.n, s.spp_done, radiance, weight, !s.uniform);
         } catch (...) {  // a segment that fails leaves no session: its film may be partly extended
@@ -2308,11 +2028,7 @@ int akr_hip_render_continue_device(akr_hip_ctx *ctx, int32_t spp, float *d_radia
         try {
             if (spp > 0) {
                 ctx->render(p, nullptr, 0, st, true);
-                if (!s.uniform) launch_count_add(ctx->d_count.p, nullptr, (uint32_t)N, (uint32_t)spp, st);
-                s.spp_done += spp;
-                s.spp_min += spp;
-                s.seeded = true;
-                s.ad.on = false;
+                advance_session(ctx, s, spp, st);
             } else {
                 ctx->serialize(st);
             }
@@ -2320,7 +2036,7 @@ int akr_hip_render_continue_device(akr_hip_ctx *ctx, int32_t spp, float *d_radia
             ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)N, d_radiance, d_weight, st); });
             HIPCHK(hipGetLastError());
             ctx->verify_weights(st, N, s.spp_done, !s.uniform);
-            if (spp > 0) ctx->unchecked_render = !ctx->verify;
+            if (spp > 0) ctx->unchecked_render = !ctx->opt.verify;
             ctx->mark_done(st);
         } catch (...) {
             ctx->drop_session();
@@ -2341,7 +2057,7 @@ void session_film_device(akr_hip_ctx *ctx, float *d_radiance, float *d_weight, h
     ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)s.n, d_radiance, d_weight, st); });
     HIPCHK(hipGetLastError());
     ctx->verify_weights(st, s.n, s.spp_done, !s.uniform);
-    if (rendered) ctx->unchecked_render = !ctx->verify;
+    if (rendered) ctx->unchecked_render = !ctx->opt.verify;
     ctx->mark_done(st);
 }
 
@@ -2656,7 +2372,7 @@ int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, c
         if (!params) throw std::runtime_error("null argument");
         if (params->spp < 0 || params->max_depth < 0) throw std::runtime_error("spp and max_depth must be >= 0");
         if (params->max_depth > 1000) throw std::runtime_error("max_depth too large");
-        if (params->spp > kMaxSessionSpp) throw std::runtime_error("render state import: spp exceeds 2^24");
+        if (params->spp > akr_hip_ctx::kSessionSppCap) throw std::runtime_error("render state import: spp exceeds 2^24");
         if (n && (!sampler || !film)) throw std::runtime_error("null argument");
         if (!ctx->cam_set) throw std::runtime_error("camera not set (call akr_hip_set_camera)");
         if (n_tiles < 0 || (n_tiles > 0 && !tiles)) throw std::runtime_error("invalid tile list");
@@ -2767,7 +2483,7 @@ const void *akr_bvh_host_wide_leaves(const akr_bvh_host *h) { return h ? h->wide
 
 int akr_hip_ray_steps(akr_hip_ctx *ctx, uint32_t *out, uint64_t n) {
     return guard(ctx, [&] {
-        if (!ctx->ray_steps || n > ctx->n_steps) throw std::runtime_error("no per-ray steps recorded for that many rays");
+        if (!ctx->opt.ray_steps || n > ctx->n_steps) throw std::runtime_error("no per-ray steps recorded for that many rays");
         if (n == 0) return;
         if (!out) throw std::runtime_error("null output");
         HIPCHK(hipMemcpyAsync(out, ctx->d_steps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -2835,7 +2551,7 @@ int akr_hip_path_profile(akr_hip_ctx *ctx, uint64_t *out, int32_t n) {
                         q.push_would_fit};
         // out[25..27]: distinct 128-B lines of the wide nodes, the leaf blob and the shading records the
         // last render with count_lines read (k_path)
-        if (n > 25 && ctx->count_lines && ctx->d_lines.p && ctx->lines_span[3]) {
+        if (n > 25 && ctx->opt.count_lines && ctx->d_lines.p && ctx->lines_span[3]) {
             std::vector<uint32_t> m(ctx->lines_span[3] / 32 + 1);
             HIPCHK(hipMemcpy(m.data(), ctx->d_lines.p, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (int r = 0; r < 3; r++)

@@ -18,8 +18,7 @@ void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, 
 void launch_store_word(const uint32_t *src, uint32_t *dst, hipStream_t st);
 void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st);
 void launch_ao_resolve(const AoResolveArgs &a, uint32_t max_items, hipStream_t st);
-// persistent path kernel forms
-enum : int { PATH_PLAIN = 0, PATH_DEFER = 1, PATH_SPEC = 2 };
+// persistent path kernel forms: PATH_PLAIN / PATH_DEFER / PATH_SPEC (akr_path_forms.h)
 void launch_path(bool count, int kind, bool tab, const PathArgs &a, uint32_t grid, hipStream_t st);
 int path_blocks_per_cu(int kind, bool tab);
 bool path_tab_fits(int32_t n_mats, int32_t n_lights);

@@ -1618,8 +1618,7 @@ __device__ __forceinline__ void path_unpark(uint32_t (*s_park)[kTraceBlock], uin
 // each wave holds the costliest and the cheapest pixels left, so lanes whose pixel ends early can
 // take the long pixels' shadow rays).  `order` (optional) maps the position to the
 // slot.  With `prio`, a wave whose fetch lies in the first `prio` / 256 of its shard (the costliest
-// pixels of a cost order) raises its issue priority, else lowers it.
-enum : uint32_t { FETCH_LINEAR = 0, FETCH_SCRAMBLE = 1, FETCH_PAIR = 2, FETCH_STRIDE = 3 };
+// pixels of a cost order) raises its issue priority, else lowers it.  (The FETCH_* names: akr_path_forms.h.)
 struct PixelFetch {
     uint32_t shard, s_lo, s_hi;
     int shards_left;
@@ -3171,35 +3170,32 @@ void launch_splat(const SplatArgs &a, uint32_t max_items, hipStream_t st) {
     if (max_items == 0) return;
     hipLaunchKernelGGL(k_splat, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
 }
-template <bool COUNT, bool TAB>
-static void launch_path_t(int kind, const PathArgs &a, uint32_t grid, hipStream_t st) {
-    if (kind == PATH_DEFER) hipLaunchKernelGGL((k_path_defer<COUNT, TAB>), dim3(grid), dim3(kTraceBlock), 0, st, a);
-    else if (kind == PATH_SPEC) hipLaunchKernelGGL((k_path_spec<COUNT, TAB>), dim3(grid), dim3(kTraceBlock), 0, st, a);
-    else hipLaunchKernelGGL((k_path<COUNT, TAB>), dim3(grid), dim3(kTraceBlock), 0, st, a);
+// The persistent path kernel for (kind, count, tab).  The compiler emits the instantiations in the order
+// they are named here, which is the order the code object has always held them in.
+using PathKernel = void (*)(PathArgs);
+static PathKernel path_kernel(int kind, bool count, bool tab) {
+    if (count && tab) {
+        if (kind == PATH_DEFER) return k_path_defer<true, true>;
+        if (kind == PATH_SPEC) return k_path_spec<true, true>;
+        return k_path<true, true>;
+    }
+    if (count) {
+        if (kind == PATH_DEFER) return k_path_defer<true, false>;
+        if (kind == PATH_SPEC) return k_path_spec<true, false>;
+        return k_path<true, false>;
+    }
+    if (kind == PATH_SPEC) return tab ? k_path_spec<false, true> : k_path_spec<false, false>;
+    if (kind == PATH_DEFER) return tab ? k_path_defer<false, true> : k_path_defer<false, false>;
+    return tab ? k_path<false, true> : k_path<false, false>;
 }
 void launch_path(bool count, int kind, bool tab, const PathArgs &a, uint32_t grid, hipStream_t st) {
     if (grid == 0) return;
     if (tab && !path_tab_fits(a.sc.n_mats, a.sc.n_lights)) tab = false;  // the LDS copy must hold every record
-    if (count) {
-        if (tab) launch_path_t<true, true>(kind, a, grid, st);
-        else launch_path_t<true, false>(kind, a, grid, st);
-    } else {
-        if (tab) launch_path_t<false, true>(kind, a, grid, st);
-        else launch_path_t<false, false>(kind, a, grid, st);
-    }
+    hipLaunchKernelGGL(path_kernel(kind, count, tab), dim3(grid), dim3(kTraceBlock), 0, st, a);
 }
 int path_blocks_per_cu(int kind, bool tab) {
     int nb = 0;
-    hipError_t e;
-    if (kind == PATH_SPEC)
-        e = tab ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path_spec<false, true>, kTraceBlock, 0)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path_spec<false, false>, kTraceBlock, 0);
-    else if (kind == PATH_DEFER)
-        e = tab ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path_defer<false, true>, kTraceBlock, 0)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path_defer<false, false>, kTraceBlock, 0);
-    else
-        e = tab ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path<false, true>, kTraceBlock, 0)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path<false, false>, kTraceBlock, 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(kind, false, tab), kTraceBlock, 0);
     if (e != hipSuccess || nb <= 0) nb = 1;
     return nb;
 }
