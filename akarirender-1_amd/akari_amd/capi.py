@@ -116,6 +116,17 @@ class AdaptiveInfo(C.Structure):
                 ("samples", C.c_uint64), ("strips", C.c_uint64), ("strips_at_cap", C.c_uint64)]
 
 
+class FeatureParams(C.Structure):
+    _fields_ = [("spp", C.c_int32), ("flags", C.c_int32)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_color", C.c_float), ("flags", C.c_int32), ("_pad", C.c_int32 * 2)]
+
+
+FEATURE_FLOATS = 12   # per pixel: albedo rgb, hits, normal xyz, t, position xyz, 0 (sums over the feature samples)
+DENOISE_NO_DEMODULATE = 1
 STRIP = 64   # slots per strip of the adaptive convergence test (packed tile order)
 MAX_SESSION_SPP = 1 << 24   # a slot's weight is an f32 count of its samples
 TEX_CONSTANT, TEX_IMAGE = 0, 1
@@ -206,6 +217,11 @@ EXPORTS = {
                                          C.POINTER(AdaptiveInfo), C.POINTER(C.c_int32)]),
     "akr_hip_adaptive_step": (C.c_int, [_P, C.POINTER(AdaptiveInfo), C.POINTER(C.c_int32)]),
     "akr_hip_adaptive_error": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "akr_hip_render_features": (C.c_int, [_P, C.POINTER(FeatureParams), _P, C.c_int32, _P]),
+    "akr_hip_render_features_device": (C.c_int, [_P, C.POINTER(FeatureParams), _P, C.c_int32, _P, _P,
+                                                 C.POINTER(C.c_uint64)]),
+    "akr_hip_denoise": (C.c_int, [_P, C.POINTER(DenoiseParams), C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "akr_hip_denoise_device": (C.c_int, [_P, C.POINTER(DenoiseParams), C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -627,6 +643,54 @@ class HipContext:
         act = np.zeros(n, np.uint8)
         self._check(self.lib.akr_hip_adaptive_error(self.h, _ptr(err), _ptr(act), n))
         return err, act
+
+    # ---- feature buffers and the a-trous filter of the film (include/akr_hip.h)
+
+    def render_features(self, spp, tiles, width, height, exact_cull=False, features=None):
+        """The feature pass (akr_hip_render_features): `spp` camera samples per pixel of `tiles`, added
+        into a full-frame [H, W, 12] array of sums (denoise.split_features turns it into images)."""
+        if features is None:
+            features = np.zeros((height, width, FEATURE_FLOATS), np.float32)
+        assert features.dtype == np.float32 and features.flags.c_contiguous
+        assert features.size == FEATURE_FLOATS * width * height
+        p = FeatureParams(int(spp), PT_EXACT_CULL if exact_cull else 0)
+        arr, n = self._rects(tiles)
+        self._check(self.lib.akr_hip_render_features(self.h, C.byref(p), _arr_ptr(arr), n, _ptr(features)))
+        return features
+
+    def render_features_device(self, spp, tiles, d_features: int, stream: int = 0, exact_cull=False):
+        """Device form: packed records (12 floats per slot, tile order) overwrite `d_features`; returns
+        the slot count."""
+        p = FeatureParams(int(spp), PT_EXACT_CULL if exact_cull else 0)
+        arr, n = self._rects(tiles)
+        npx = C.c_uint64(0)
+        self._check(self.lib.akr_hip_render_features_device(self.h, C.byref(p), _arr_ptr(arr), n,
+                                                            C.c_void_p(d_features), C.c_void_p(stream), C.byref(npx)))
+        return npx.value
+
+    def denoise(self, radiance, weight, features, **params):
+        """The a-trous filter (akr_hip_denoise) of a film [H, W, 3] / [H, W] guided by the feature sums
+        [H, W, 12]; returns the filtered mean colour [H, W, 3].  params: akari_amd.denoise.params()."""
+        from . import denoise as dn
+        p = dn.params(**params)   # refused before the device is touched
+        radiance = np.ascontiguousarray(radiance, np.float32)
+        weight = np.ascontiguousarray(weight, np.float32)
+        features = np.ascontiguousarray(features, np.float32)
+        dn.check_shapes(radiance, weight, features)
+        h, w = weight.shape
+        out = np.zeros((h, w, 3), np.float32)
+        self._check(self.lib.akr_hip_denoise(self.h, C.byref(p), w, h, _ptr(radiance), _ptr(weight), _ptr(features),
+                                             _ptr(out)))
+        return out
+
+    def denoise_device(self, width, height, d_radiance: int, d_weight: int, d_features: int, d_out_rgb: int,
+                       stream: int = 0, **params):
+        """Device form: frame-ordered device pointers, enqueued on `stream`."""
+        from . import denoise as dn
+        p = dn.params(**params)
+        self._check(self.lib.akr_hip_denoise_device(self.h, C.byref(p), int(width), int(height), C.c_void_p(d_radiance),
+                                                    C.c_void_p(d_weight), C.c_void_p(d_features),
+                                                    C.c_void_p(d_out_rgb), C.c_void_p(stream)))
 
     def ray_steps(self, n: int) -> np.ndarray:
         """Per-ray traversal iterations of the last standalone trace (option "ray_steps")."""

@@ -18,6 +18,11 @@ saved after each pass, or a saved one is continued up to the scene's spp.
 The third line renders a Path scene adaptively: N samples for every pixel (default
 16), then passes only over the 64-pixel strips whose error is above THRESHOLD, up to the scene's spp
 (the cap); --spp-map writes each pixel's sample count.  Checkpoints do not hold an adaptive film.
+       ... --denoise [--denoise-iters N] [--feature-spp N] [--aov PREFIX]
+With any of the lines above, --denoise writes the film filtered by the edge-avoiding a-trous filter
+ as the output, previews included: the feature pass (albedo, normal, depth; N camera
+samples per pixel, default 2) runs once per run, the filter once per written film.  --aov writes
+PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm, with or without --denoise.
 """
 from __future__ import annotations
 
@@ -30,7 +35,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import capi, film, progressive, scene
+from . import capi, denoise, film, progressive, scene
 from .dist import tile_grid
 
 
@@ -39,8 +44,49 @@ def _tiles(sc: scene.Scene, tile_size: int) -> List[Tuple[int, int, int, int]]:
     return tile_grid(w, h, max(1, int(tile_size)))
 
 
-def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), **build_kw) -> Tuple[np.ndarray, np.ndarray]:
-    """Render `sc` with its integrator node; returns the film (radiance [H,W,3], weight [H,W])."""
+class FilmPost:
+    """--denoise / --aov: the feature pass once per run on the context that holds the
+    scene, and the filter of every film handed to finish().  `image` is the last filtered mean colour
+    [H, W, 3] (None without --denoise), `features` the feature sums [H, W, 12]."""
+
+    def __init__(self, do_denoise: bool, iterations: Optional[int] = None, feature_spp: Optional[int] = None,
+                 per_pass: bool = False):
+        self.do_denoise = bool(do_denoise)
+        self.params = {} if iterations is None else {"iterations": int(iterations)}
+        denoise.params(**self.params)   # refused here, before a device is touched
+        self.feature_spp = denoise.DEFAULT_FEATURE_SPP if feature_spp is None else int(feature_spp)
+        if self.feature_spp < 1:
+            raise ValueError("the feature pass needs at least one sample")
+        self.per_pass = bool(per_pass) and self.do_denoise
+        self.features = self.image = self._film = None
+
+    def bind(self, tiles, width: int, height: int, demodulate: bool = True) -> None:
+        """The run's tile list and frame; demodulate=False for films that are not albedo times lighting (AO)."""
+        self.tiles, self.width, self.height = tiles, int(width), int(height)
+        if not demodulate:
+            self.params["demodulate"] = False
+
+    def finish(self, ctx: "capi.HipContext", radiance, weight) -> None:
+        if self._film is radiance:   # this film is done already (the last pass's preview)
+            return
+        if self.features is None:
+            self.features = ctx.render_features(self.feature_spp, self.tiles, self.width, self.height)
+        if self.do_denoise:
+            self.image = ctx.denoise(radiance, weight, self.features, **self.params)
+        self._film = radiance
+
+    def write_aov(self, prefix: str) -> None:
+        albedo, normal, depth, _ = denoise.split_features(self.features)
+        one = np.ones(depth.shape, np.float32)
+        film.write_pfm(prefix + ".albedo.pfm", albedo, one)
+        film.write_pfm(prefix + ".normal.pfm", normal, one)
+        film.write_pfm(prefix + ".depth.pfm", np.repeat(depth[..., None], 3, axis=-1), one)
+
+
+def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[FilmPost] = None,
+                 **build_kw) -> Tuple[np.ndarray, np.ndarray]:
+    """Render `sc` with its integrator node; returns the film (radiance [H,W,3], weight [H,W]).  With
+    `post`, the features and the filter run on the first device after the film is gathered."""
     cs = scene.compile_scene(sc)
     w, h = (int(v) for v in sc.camera.resolution)
     it = sc.integrator
@@ -51,13 +97,20 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), **build_kw) -> 
         if isinstance(it, scene.AOIntegrator):
             if len(ctxs) != 1:
                 raise ValueError("the AO integrator renders on one device")
-            return ctxs[0].render_ao(it.spp, _tiles(sc, 16), w, h, occlude=it.occlude)
-        if isinstance(it, scene.PathIntegrator):
+            tiles = _tiles(sc, 16)
+            rad, wt = ctxs[0].render_ao(it.spp, tiles, w, h, occlude=it.occlude)
+        elif isinstance(it, scene.PathIntegrator):
             tiles = _tiles(sc, it.tile_size)
             if len(ctxs) == 1:
-                return ctxs[0].render(it.spp, it.max_depth, tiles, w, h, ray_clamp=it.ray_clamp)
-            return capi.render_node(ctxs, it.spp, it.max_depth, tiles, w, h, ray_clamp=it.ray_clamp)
-        raise ValueError(f"integrator {type(it).__name__} is not supported on gpu")
+                rad, wt = ctxs[0].render(it.spp, it.max_depth, tiles, w, h, ray_clamp=it.ray_clamp)
+            else:
+                rad, wt = capi.render_node(ctxs, it.spp, it.max_depth, tiles, w, h, ray_clamp=it.ray_clamp)
+        else:
+            raise ValueError(f"integrator {type(it).__name__} is not supported on gpu")
+        if post is not None:
+            post.bind(tiles, w, h, demodulate=isinstance(it, scene.PathIntegrator))
+            post.finish(ctxs[0], rad, wt)
+        return rad, wt
     finally:
         for c in ctxs:
             c.close()
@@ -65,7 +118,7 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), **build_kw) -> 
 
 def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optional[int] = None,
                              on_pass=None, time_budget: Optional[float] = None, checkpoint=None, resume=None,
-                             **build_kw) -> Tuple[np.ndarray, np.ndarray, int]:
+                             post: Optional[FilmPost] = None, **build_kw) -> Tuple[np.ndarray, np.ndarray, int]:
     """Render a Path scene in passes on one device; returns (radiance, weight, spp_done).
 
     pass_spp: samples per pass (default: each pass doubles the samples done); on_pass(spp_done,
@@ -91,20 +144,28 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
         if ck is not None:
             ck.restore(ctx, cs, tiles)
 
+        if post is not None:
+            post.bind(tiles, w, h)
+
         def each_pass(done, rad, wt):
             if checkpoint is not None:
                 progressive.Checkpoint.capture(ctx, cs, tiles).save(checkpoint)
+            if post is not None and post.per_pass:   # the feature pass and the filter keep the session
+                post.finish(ctx, rad, wt)
             return on_pass(done, rad, wt) if on_pass is not None else None
 
-        return progressive.render_progressive(ctx, it.spp, it.max_depth, tiles, w, h,
-                                              schedule=pass_spp if pass_spp is not None else "double",
-                                              on_pass=each_pass, time_budget=time_budget, ray_clamp=it.ray_clamp,
-                                              resume=ck is not None)
+        out = progressive.render_progressive(ctx, it.spp, it.max_depth, tiles, w, h,
+                                             schedule=pass_spp if pass_spp is not None else "double",
+                                             on_pass=each_pass, time_budget=time_budget, ray_clamp=it.ray_clamp,
+                                             resume=ck is not None)
+        if post is not None:
+            post.finish(ctx, out[0], out[1])
+        return out
 
 
 def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, min_spp: int = 16,
                           pass_spp: Optional[int] = None, on_pass=None, time_budget: Optional[float] = None,
-                          **build_kw):
+                          post: Optional[FilmPost] = None, **build_kw):
     """Render a Path scene adaptively on one device; returns (radiance, weight, info).  The integrator's
     spp is the cap; weight holds each pixel's sample count (progressive.render_adaptive)."""
     it = sc.integrator
@@ -115,9 +176,20 @@ def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, mi
     w, h = (int(v) for v in sc.camera.resolution)
     with capi.HipContext(device) as ctx:
         scene.upload_scene(ctx, cs, **build_kw)
-        return progressive.render_adaptive(ctx, it.spp, it.max_depth, _tiles(sc, it.tile_size), w, h, threshold,
-                                           min_spp=min_spp, pass_spp=pass_spp or 0, on_pass=on_pass,
-                                           time_budget=time_budget, ray_clamp=it.ray_clamp)
+        tiles = _tiles(sc, it.tile_size)
+        each = on_pass
+        if post is not None:
+            post.bind(tiles, w, h)
+            if on_pass is not None and post.per_pass:
+                def each(info, rad, wt):
+                    post.finish(ctx, rad, wt)
+                    return on_pass(info, rad, wt)
+        out = progressive.render_adaptive(ctx, it.spp, it.max_depth, tiles, w, h, threshold,
+                                          min_spp=min_spp, pass_spp=pass_spp or 0, on_pass=each,
+                                          time_budget=time_budget, ray_clamp=it.ray_clamp)
+        if post is not None:
+            post.finish(ctx, out[0], out[1])
+        return out
 
 
 def write_spp_map(path: str, weight: np.ndarray) -> None:
@@ -154,7 +226,32 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     help="with --adaptive: samples every pixel gets before the first test (default 16)")
     ap.add_argument("--spp-map", default=None, metavar="FILE.pfm",
                     help="with --adaptive: write each pixel's sample count")
+    ap.add_argument("--denoise", action="store_true",
+                    help="write the film filtered by the edge-avoiding a-trous filter (previews included)")
+    ap.add_argument("--denoise-iters", type=int, default=None, metavar="N",
+                    help=f"with --denoise: filter iterations, 1..{denoise.MAX_ITERATIONS} "
+                         f"(default {denoise.DEFAULTS['iterations']})")
+    ap.add_argument("--feature-spp", type=int, default=None, metavar="N",
+                    help=f"with --denoise or --aov: camera samples per pixel of the feature pass "
+                         f"(default {denoise.DEFAULT_FEATURE_SPP})")
+    ap.add_argument("--aov", default=None, metavar="PREFIX",
+                    help="write PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm")
     args = ap.parse_args(argv)
+    if args.denoise_iters is not None:  # refused before the scene is read
+        if not args.denoise:
+            ap.error("--denoise-iters needs --denoise")
+        if not 1 <= args.denoise_iters <= denoise.MAX_ITERATIONS:
+            ap.error(f"--denoise-iters needs 1..{denoise.MAX_ITERATIONS}")
+    if args.feature_spp is not None:
+        if not args.denoise and args.aov is None:
+            ap.error("--feature-spp needs --denoise or --aov")
+        if args.feature_spp < 1:
+            ap.error("--feature-spp needs at least one sample")
+    if args.aov is not None and not args.aov:
+        ap.error("--aov needs a file prefix")
+    post = None
+    if args.denoise or args.aov is not None:
+        post = FilmPost(args.denoise, args.denoise_iters, args.feature_spp, per_pass=args.preview)
     if args.adaptive is not None:  # refused before the scene is read
         if args.checkpoint is not None or args.resume is not None:
             ap.error("--adaptive cannot be combined with --checkpoint or --resume: a checkpoint holds a film "
@@ -184,10 +281,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  f"the scene's is {type(sc.integrator).__name__}")
     out = args.out or sc.output
     t0 = time.time()
+
+    def write_out(rad, wt):
+        """The output image: the filtered film with --denoise, else the film."""
+        if post is not None and post.image is not None:
+            write_film(out, post.image, np.ones(post.image.shape[:2], np.float32))
+        else:
+            write_film(out, rad, wt)
+
     if args.adaptive is not None:
         def show_adaptive(info, rad, wt):
             if args.preview:
-                write_film(out, rad, wt)
+                write_out(rad, wt)
                 print(f"pass {info['passes']} to {info['spp_max']} spp, {info['samples']} samples: "
                       f"{time.time() - t0:.2f}s -> {out}", flush=True)
 
@@ -195,7 +300,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             per_pass = args.preview or args.time_budget is not None
             rad, wt, info = render_scene_adaptive(sc, args.adaptive, 0, min_spp=args.min_spp, pass_spp=args.pass_spp,
                                                   on_pass=show_adaptive if per_pass else None,
-                                                  time_budget=args.time_budget)
+                                                  time_budget=args.time_budget, post=post)
         except ValueError as e:
             ap.error(str(e))
         done = f"{info['spp_min']}..{info['spp_max']} ({info['samples']} samples in {info['passes']} passes)"
@@ -204,19 +309,21 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     elif passes:
         def show(done, rad, wt):
             if args.preview:
-                write_film(out, rad, wt)
+                write_out(rad, wt)
                 print(f"pass to {done} spp: {time.time() - t0:.2f}s -> {out}", flush=True)
 
         try:
             rad, wt, done = render_scene_progressive(sc, 0, pass_spp=args.pass_spp, on_pass=show,
                                                      time_budget=args.time_budget, checkpoint=args.checkpoint,
-                                                     resume=args.resume)
+                                                     resume=args.resume, post=post)
         except progressive.CheckpointError as e:
             ap.error(str(e))
     else:
-        rad, wt = render_scene(sc, devices=list(range(args.gpus)))
+        rad, wt = render_scene(sc, devices=list(range(args.gpus)), post=post)
         done = sc.integrator.spp
-    write_film(out, rad, wt)
+    write_out(rad, wt)
+    if args.aov is not None:
+        post.write_aov(args.aov)
     print(f"{type(sc.integrator).__name__} {sc.camera.resolution[0]}x{sc.camera.resolution[1]} "
           f"spp {done}: {time.time() - t0:.2f}s -> {out}")
     return 0

@@ -325,6 +325,30 @@ class HipPathTracer {
         return {lo, hi};
     }
 
+    // Feature buffers and the a-trous filter of the film (include/akr_hip.h); both keep the
+    // session.  render_features: `feature_spp` camera samples per pixel of the film's tiles; `features` is
+    // cleared and then holds the 12 sums per pixel (albedo rgb, hits, normal xyz, t, position xyz, 0).
+    void render_features(const HipAccelerator &scene, const Film &film, int feature_spp, std::vector<float> &features) const {
+        std::vector<akr_rect> tiles;
+        for (int y = 0; y < film.height; y += tile_size)
+            for (int x = 0; x < film.width; x += tile_size) tiles.push_back({x, y, x + tile_size, y + tile_size});
+        features.assign(12 * (size_t)film.width * film.height, 0.0f);
+        akr_feature_params p{feature_spp, 0};
+        check(scene.handle(), akr_hip_render_features(scene.handle(), &p, tiles.data(), (int32_t)tiles.size(), features.data()),
+              "render_features");
+    }
+    // the film filtered with `p`, guided by `features`: the mean colour, 3 floats per pixel
+    static akr_denoise_params denoise_defaults() { return akr_denoise_params{5, 5, 0.02f, 0.3f, 0.5f, 0, {0, 0}}; }
+    void denoise(const HipAccelerator &scene, const Film &film, const std::vector<float> &features,
+                 std::vector<float> &out_rgb, const akr_denoise_params &p = denoise_defaults()) const {
+        if (features.size() != 12 * film.weight.size()) throw std::runtime_error("denoise: twelve feature sums per pixel");
+        out_rgb.assign(film.radiance.size(), 0.0f);
+        check(scene.handle(),
+              akr_hip_denoise(scene.handle(), &p, film.width, film.height, film.radiance.data(), film.weight.data(),
+                              features.data(), out_rgb.data()),
+              "denoise");
+    }
+
     // Multi-GPU in one process (akr_hip_render_node): tile j on accelerators[j % n], one per device,
     // each built from the same scene; the merged film equals render() on one of them.
     void render_node(const std::vector<const HipAccelerator *> &accels, Film &film) const {

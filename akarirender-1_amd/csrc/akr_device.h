@@ -219,6 +219,17 @@ struct AoResolveArgs {
     float occlude;
 };
 
+// Feature pass: one camera sample of every slot added to its 12-float record,
+// (albedo rgb, hits | normal xyz, t | position xyz, 0) as three float4.
+struct FeatureArgs {
+    SceneDev sc;
+    const float4 *ray_in;          // 2 per slot: the sample's camera ray
+    const float4 *hit_in;          // per slot: (t, u, v, gid bits)
+    const uint32_t *seed;          // per slot: the slot's chain after the camera ray (read as a copy)
+    float4 *acc;                   // 3 per slot
+    uint32_t n;
+};
+
 struct RaygenArgs {
     CameraDev cam;
     const uint32_t *pixel;         // per slot: x | y << 16

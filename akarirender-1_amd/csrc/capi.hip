@@ -1393,6 +1393,122 @@ struct akr_hip_ctx {
         join_streams(st);
         return N;
     }
+
+    // ---- feature pass and film filter.  Both keep the session: the pass has its own
+    // tile list, pixel list, chain states and accumulators, and borrows only the ray and hit queues (when
+    // they are large enough: growing them would reallocate the session's film with them), the traversal
+    // overflow stack and the standalone trace's fetch counters.
+    std::vector<uint4> ft_tiles;
+    uint64_t ft_n = 0;
+    DBuf<uint4> d_ft_tiles;
+    DBuf<uint32_t> d_ft_pixel, d_ft_seed;
+    DBuf<float4> d_ft_acc, d_ft_ray, d_ft_hit;
+    DBuf<float4> d_dn_guide, d_dn_I[2];
+    DBuf<float> d_dn_in, d_dn_out;
+
+    // spp camera samples of every slot of `tiles` into d_ft_acc (3 float4 per slot) on `st`; returns the slots
+    uint64_t render_features(const akr_feature_params &p, const akr_rect *tiles, int32_t n_tiles, hipStream_t st) {
+        if (p.spp < 1) throw std::runtime_error("feature pass: spp must be >= 1");
+        if (p.flags & ~AKR_PT_EXACT_CULL) throw std::runtime_error("feature pass: flags must be 0 or AKR_PT_EXACT_CULL");
+        require_ready();
+        if (!cam_set) throw std::runtime_error("camera not set (call akr_hip_set_camera)");
+        if (n_tiles < 0 || (n_tiles > 0 && !tiles)) throw std::runtime_error("invalid tile list");
+        ft_tiles.clear();
+        uint64_t N = 0;
+        for (int k = 0; k < n_tiles; k++) {  // clipped, non-empty tiles in order, as setup_pixels lays them out
+            const int x0 = std::max(0, tiles[k].x0), y0 = std::max(0, tiles[k].y0);
+            const int x1 = std::min(cam.width, tiles[k].x1), y1 = std::min(cam.height, tiles[k].y1);
+            if (x1 <= x0 || y1 <= y0) continue;
+            if (N >= (1ull << 31)) break;  // rejected below
+            ft_tiles.push_back(make_uint4((uint32_t)x0, (uint32_t)y0, (uint32_t)(x1 - x0), (uint32_t)N));
+            N += (uint64_t)(x1 - x0) * (uint64_t)(y1 - y0);
+        }
+        if (N >= (1ull << 31)) throw std::runtime_error("too many pixels in one feature pass");
+        ft_n = N;
+        serialize(st);
+        if (N == 0) {
+            mark_done(st);
+            return 0;
+        }
+        d_ft_pixel.reserve(N);
+        d_ft_seed.reserve(N);
+        d_ft_acc.reserve(3 * N);
+        float4 *rays = d_ray0.p, *hits = d_hit.p;
+        if (N > cap) {
+            d_ft_ray.reserve(2 * N);
+            d_ft_hit.reserve(N);
+            rays = d_ft_ray.p;
+            hits = d_ft_hit.p;
+        }
+        d_ft_tiles.upload(ft_tiles.data(), ft_tiles.size(), st);
+        launch_expand_pixels(d_ft_tiles.p, (uint32_t)ft_tiles.size(), (uint32_t)N, d_ft_pixel.p, st);
+        HIPCHK(hipMemsetAsync(d_ft_acc.p, 0, 3 * N * sizeof(float4), st));
+        const bool tight = !(opt.exact_cull || (p.flags & AKR_PT_EXACT_CULL));
+        for (int s = 0; s < p.spp; s++) {
+            timed("feature_rays", st, [&] { launch_feature_rays(cam, d_ft_pixel.p, (uint32_t)N, d_ft_seed.p, s == 0, rays, st); });
+            HIPCHK(hipMemsetAsync(d_work.p, 0, kTraceWords * sizeof(uint32_t), st));
+            TraceArgs t = trace_args(d_work.p);
+            t.rays = rays;
+            t.n = (uint32_t)N;
+            t.hits = hits;
+            timed("trace_closest", st, [&] { trace_launch(TRACE_CLOSEST, tight, t, N, st); });
+            FeatureArgs fa{};
+            fa.sc = scene_dev();
+            fa.ray_in = rays;
+            fa.hit_in = hits;
+            fa.seed = d_ft_seed.p;
+            fa.acc = d_ft_acc.p;
+            fa.n = (uint32_t)N;
+            timed("features", st, [&] { launch_feature_shade(fa, st); });
+        }
+        HIPCHK(hipGetLastError());
+        mark_done(st);
+        return N;
+    }
+
+    static void check_denoise(const akr_denoise_params *p, int32_t width, int32_t height) {
+        if (!p) throw std::runtime_error("denoise: null parameters");
+        if (width <= 0 || height <= 0) throw std::runtime_error("denoise: the frame is empty (W * H == 0)");
+        if ((uint64_t)width * (uint64_t)height >= (1ull << 31)) throw std::runtime_error("denoise: too many pixels");
+        if (p->iterations < 1 || p->iterations > 8) throw std::runtime_error("denoise: iterations must be in 1..8");
+        if (p->normal_squarings < 0 || p->normal_squarings > 8)
+            throw std::runtime_error("denoise: normal_squarings must be in 0..8");
+        if (!(p->sigma_depth > 0.0f) || !(p->sigma_albedo > 0.0f))
+            throw std::runtime_error("denoise: sigma_depth and sigma_albedo must be > 0");
+        if (p->sigma_color != p->sigma_color) throw std::runtime_error("denoise: sigma_color is NaN");
+        if (p->flags & ~AKR_DENOISE_NO_DEMODULATE) throw std::runtime_error("denoise: unknown flags");
+    }
+
+    // the filter on frame-ordered device buffers, enqueued on `st`
+    void denoise(const akr_denoise_params &p, int32_t width, int32_t height, const float *rad, const float *w,
+                 const float *feat, float *out, hipStream_t st) {
+        const uint32_t n = (uint32_t)((uint64_t)width * (uint64_t)height);
+        d_dn_guide.reserve(3 * (size_t)n);
+        d_dn_I[0].reserve(n);
+        d_dn_I[1].reserve(n);
+        const bool dm = !(p.flags & AKR_DENOISE_NO_DEMODULATE);
+        serialize(st);
+        timed("denoise_prep", st, [&] { launch_denoise_prep(rad, w, feat, n, dm, d_dn_guide.p, d_dn_I[0].p, st); });
+        for (int i = 0; i < p.iterations; i++) {
+            DenoiseArgs a{};
+            a.guide = d_dn_guide.p;
+            a.in = d_dn_I[i & 1].p;
+            a.out = d_dn_I[(i + 1) & 1].p;
+            a.width = width;
+            a.height = height;
+            a.step = 1 << i;
+            a.squarings = p.normal_squarings;
+            a.color_stop = p.sigma_color > 0.0f ? 1 : 0;
+            a.sigma_depth = p.sigma_depth;
+            a.sigma_albedo = p.sigma_albedo;
+            const float sc = p.sigma_color * (1.0f / (float)(1 << i));
+            a.sc2 = sc * sc;
+            timed("denoise", st, [&] { launch_denoise_atrous(a, st); });
+        }
+        timed("denoise_finish", st, [&] { launch_denoise_finish(d_dn_guide.p, d_dn_I[p.iterations & 1].p, n, dm, out, st); });
+        HIPCHK(hipGetLastError());
+        mark_done(st);
+    }
 };
 
 namespace {
@@ -1959,6 +2075,73 @@ int akr_hip_render_ao(akr_hip_ctx *ctx, const akr_ao_params *params, const akr_r
     return guard(ctx, [&] {
         if (!params || !radiance || !weight) throw std::runtime_error("null argument");
         merge_film(ctx, ctx->render_ao(*params, tiles, n_tiles, ctx->stream), params->spp, radiance, weight);
+    });
+}
+
+int akr_hip_render_features(akr_hip_ctx *ctx, const akr_feature_params *params, const akr_rect *tiles, int32_t n_tiles,
+                            float *features) {
+    return guard(ctx, [&] {
+        if (!params || !features) throw std::runtime_error("null argument");
+        hipStream_t st = ctx->stream;
+        const uint64_t N = ctx->render_features(*params, tiles, n_tiles, st);
+        if (N == 0) return;
+        std::vector<float> rec(12 * N);
+        HIPCHK(hipMemcpyAsync(rec.data(), ctx->d_ft_acc.p, rec.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t W = (uint64_t)ctx->cam.width;
+        for (const uint4 &t : ctx->ft_tiles) {  // slot order: tiles in order, row-major inside a tile
+            const uint64_t end = &t == &ctx->ft_tiles.back() ? N : (&t)[1].w;
+            for (uint64_t i = t.w; i < end; i++) {
+                const uint64_t local = i - t.w;
+                float *dst = features + 12 * ((t.x + local % t.z) + (t.y + local / t.z) * W);
+                for (int c = 0; c < 12; c++) dst[c] += rec[12 * i + c];
+            }
+        }
+    });
+}
+
+int akr_hip_render_features_device(akr_hip_ctx *ctx, const akr_feature_params *params, const akr_rect *tiles,
+                                   int32_t n_tiles, float *d_features, void *stream, uint64_t *n_pixels) {
+    return guard(ctx, [&] {
+        if (!params || !d_features) throw std::runtime_error("null argument");
+        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        const uint64_t N = ctx->render_features(*params, tiles, n_tiles, st);
+        if (n_pixels) *n_pixels = N;
+        if (N == 0) return;
+        HIPCHK(hipMemcpyAsync(d_features, ctx->d_ft_acc.p, 12 * N * sizeof(float), hipMemcpyDeviceToDevice, st));
+        ctx->mark_done(st);
+    });
+}
+
+int akr_hip_denoise(akr_hip_ctx *ctx, const akr_denoise_params *params, int32_t width, int32_t height,
+                    const float *radiance, const float *weight, const float *features, float *out_rgb) {
+    return guard(ctx, [&] {
+        if (!radiance || !weight || !features || !out_rgb) throw std::runtime_error("denoise: null argument");
+        akr_hip_ctx::check_denoise(params, width, height);
+        const size_t n = (size_t)width * (size_t)height;
+        hipStream_t st = ctx->stream;
+        ctx->serialize(st);  // the staging buffers are shared by every denoise of the context
+        ctx->d_dn_in.reserve(16 * n);
+        ctx->d_dn_out.reserve(3 * n);
+        float *d_rad = ctx->d_dn_in.p, *d_w = d_rad + 3 * n, *d_feat = d_rad + 4 * n;
+        HIPCHK(hipMemcpyAsync(d_rad, radiance, 3 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_w, weight, n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_feat, features, 12 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        ctx->denoise(*params, width, height, d_rad, d_w, d_feat, ctx->d_dn_out.p, st);
+        HIPCHK(hipMemcpyAsync(out_rgb, ctx->d_dn_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
+        ctx->mark_done(st);
+        HIPCHK(hipStreamSynchronize(st));
+    });
+}
+
+int akr_hip_denoise_device(akr_hip_ctx *ctx, const akr_denoise_params *params, int32_t width, int32_t height,
+                           const float *d_radiance, const float *d_weight, const float *d_features, float *d_out_rgb,
+                           void *stream) {
+    return guard(ctx, [&] {
+        if (!d_radiance || !d_weight || !d_features || !d_out_rgb) throw std::runtime_error("denoise: null argument");
+        akr_hip_ctx::check_denoise(params, width, height);
+        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        ctx->denoise(*params, width, height, d_radiance, d_weight, d_features, d_out_rgb, st);
     });
 }
 

@@ -58,4 +58,26 @@ void launch_probe_fill(const uint32_t *seed, uint32_t n, uint4 *probe, uint32_t 
 void launch_adaptive_test(const float4 *film, float4 *prev, uint32_t n, float threshold, float *strip_err,
                           uint8_t *strip_active, uint8_t *mask, hipStream_t st);
 
+// feature pass: sample k's camera ray of every slot from the slot's own chain
+// (seed[i], or x + y * width when `first`), and the hit's albedo / normal / depth / position sums
+void launch_feature_rays(const CameraDev &cam, const uint32_t *pixel, uint32_t n, uint32_t *seed, bool first,
+                         float4 *rays, hipStream_t st);
+void launch_feature_shade(const FeatureArgs &a, hipStream_t st);
+
+// edge-avoiding a-trous filter of the film (denoise.hip): frame-ordered buffers of n = W * H
+// pixels; guide = 3 float4 per pixel (unit normal | depth, position | 0, albedo | 0), I = (colour | state)
+struct DenoiseArgs {
+    const float4 *guide;
+    const float4 *in;
+    float4 *out;
+    int32_t width, height, step, squarings;
+    int32_t color_stop;                     // sigma_color > 0
+    float sigma_depth, sigma_albedo, sc2;   // sc2: sc * sc of this iteration, sc = sigma_color * (1 / step)
+};
+void launch_denoise_prep(const float *radiance, const float *weight, const float *features, uint32_t n, bool demodulate,
+                         float4 *guide, float4 *I, hipStream_t st);
+void launch_denoise_atrous(const DenoiseArgs &a, hipStream_t st);
+void launch_denoise_finish(const float4 *guide, const float4 *I, uint32_t n, bool demodulate, float *out_rgb,
+                           hipStream_t st);
+
 }  // namespace akr

@@ -3099,6 +3099,81 @@ __global__ __launch_bounds__(kBlock) void k_adaptive_test(const float4 *film, fl
     }
 }
 
+// -------------------------------------------------------------------------------- feature pass
+// Sample k's camera ray of every slot: the slot's own chain, four draws per ray and
+// nothing else, so sample 0 is the beauty render's first camera ray and later samples are not.
+__global__ __launch_bounds__(kBlock) void k_feature_rays(CameraDev cam, const uint32_t *pixel, uint32_t n, uint32_t *seed,
+                                                         int32_t first, float4 *rays) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t px = pixel[i];
+    const int x = (int)(px & 0xFFFFu), y = (int)(px >> 16);
+    uint32_t s = first ? (uint32_t)(x + y * cam.width) : seed[i];
+    float4 r0, r1;
+    camera_ray(cam, x, y, s, r0, r1);
+    rays[2 * (size_t)i] = r0;
+    rays[2 * (size_t)i + 1] = r1;
+    seed[i] = s;
+}
+
+// What a camera hit adds to the slot's record: 1 hit, the distance, the point, the geometric normal
+// turned towards the viewer, and the colour of the material the path tracer would shade there (the Mix
+// walk of shade_hit_tab restated, its selector the next draw of a copy of the chain).
+__global__ __launch_bounds__(kBlock) void k_feature_shade(FeatureArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float4 hv = a.hit_in[i];
+    const uint32_t gid = fbits(hv.w);
+    if (gid == kNoHit) return;  // a miss adds nothing
+    const SceneDev &s = a.sc;
+    const ShadeTri tr = s.tri[gid];
+    const int32_t mid = (int32_t)fbits(tr.a.w);
+    const float u = hv.y, v = hv.z;
+    const V3 v0{tr.a.x, tr.a.y, tr.a.z}, v1{tr.b.x, tr.b.y, tr.b.z}, v2{tr.c.x, tr.c.y, tr.c.z};
+    const V3 p = lerp3(v0, v1, v2, u, v);
+    V3 ng = normalize(cross(sub(v1, v0), sub(v2, v0)));
+    const float4 rd = a.ray_in[2 * (size_t)i + 1];
+    if (dot(ng, v3(rd.x, rd.y, rd.z)) > 0.0f) ng = neg(ng);
+    V3 alb = v3(0.0f, 0.0f, 0.0f);
+    if (mid >= 0) {  // a null material is a hit with albedo 0
+        V2 tc{0.0f, 0.0f};
+        if (s.has_image_tex) {
+            const AKR_GLOBAL float *tt = s.texcoords + 6 * (size_t)gid;
+            tc = lerp3(V2{tt[0], tt[1]}, V2{tt[2], tt[3]}, V2{tt[4], tt[5]}, u, v);
+        }
+        const AKR_GLOBAL MatDev *mat = s.mats + mid;
+        uint32_t copy = a.seed[i];
+        float sel_u = lcg_next(copy);
+        while (mat->type == AKR_MAT_MIX) {  // Material::select_material, material.h:251-268
+            const float frac = mat_x(s, mat->frac, mat->frac_img, tc);
+            if (sel_u < frac) {
+                sel_u = sel_u / frac;
+                mat = s.mats + mat->second;
+            } else {
+                sel_u = (sel_u - frac) / (1.0f - frac);
+                mat = s.mats + mat->first;
+            }
+        }
+        if (mat->type == AKR_MAT_DIFFUSE || mat->type == AKR_MAT_GLOSSY || mat->type == AKR_MAT_EMISSIVE)
+            alb = mat_rgb(s, mat->color, mat->color_img, tc);
+    }
+    float4 r0 = a.acc[3 * (size_t)i], r1 = a.acc[3 * (size_t)i + 1], r2 = a.acc[3 * (size_t)i + 2];
+    r0.x += alb.x;
+    r0.y += alb.y;
+    r0.z += alb.z;
+    r0.w += 1.0f;
+    r1.x += ng.x;
+    r1.y += ng.y;
+    r1.z += ng.z;
+    r1.w += hv.x;
+    r2.x += p.x;
+    r2.y += p.y;
+    r2.z += p.z;
+    a.acc[3 * (size_t)i] = r0;
+    a.acc[3 * (size_t)i + 1] = r1;
+    a.acc[3 * (size_t)i + 2] = r2;
+}
+
 // ------------------------------------------------------------------------------------ launch
 static inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
@@ -3263,6 +3338,13 @@ void launch_adaptive_test(const float4 *film, float4 *prev, uint32_t n, float th
 void launch_unpack(const float4 *film, uint32_t n, float *rad, float *w, hipStream_t st) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_unpack_film, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, n, rad, w);
+}
+void launch_feature_rays(const CameraDev &cam, const uint32_t *pixel, uint32_t n, uint32_t *seed, bool first,
+                         float4 *rays, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_feature_rays, dim3(blocks_for(n)), dim3(kBlock), 0, st, cam, pixel, n, seed, first ? 1 : 0, rays);
+}
+void launch_feature_shade(const FeatureArgs &a, hipStream_t st) {
+    if (a.n) hipLaunchKernelGGL(k_feature_shade, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
 }
 
 }  // namespace akr

@@ -48,8 +48,8 @@ extern "C" {
 
 /* 2: akr_trace_counts gained deep_rays[3]; akr_pixel_probe / akr_hip_pixel_probe added
  * 3: akr_trace_counts gained leaf_tests[3]
- *    (still 3 with the render session and adaptive sampling calls below: they only add exports and
- *    change no struct layout) */
+ *    (still 3 with the render session, adaptive sampling, feature and filter calls below: they only
+ *    add exports and change no struct layout) */
 #define AKR_HIP_API_VERSION 3
 
 typedef struct akr_hip_ctx akr_hip_ctx;
@@ -307,6 +307,8 @@ int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const a
  *    "no render session to continue"; the context stays usable.  A continue that fails while
  *    rendering ends the session (its film may be partly extended).
  *  - akr_hip_trace, akr_hip_trace_device and the query calls keep it.
+ *  - akr_hip_render_features, akr_hip_render_features_device, akr_hip_denoise and akr_hip_denoise_device keep
+ *    it: they touch neither the film, the sampler states, the per-slot counts nor the session record.
  *  - akr_hip_set_option between segments is allowed, and may switch the render form, the cost order
  *    and exact_cull: all give the same bits.
  *  - spp = 0 renders nothing and returns the totals.  A total above 2^24 samples per slot is refused
@@ -420,6 +422,77 @@ int akr_hip_adaptive_step(akr_hip_ctx *ctx, akr_adaptive_info *info, int32_t *mo
  * each strip's error E and whether it is still active.  A strip that stopped earlier keeps the error
  * it stopped with.  Fails when the session ran no test. */
 int akr_hip_adaptive_error(akr_hip_ctx *ctx, float *strip_error, uint8_t *strip_active, uint64_t n_strips);
+
+/* ---- Feature buffers and the edge-avoiding a-trous filter of the film.
+ *
+ * Feature pass.  Every film slot of the tile list (clipped, packed tile order, exactly as in
+ * akr_hip_render_device) gets `spp` camera rays from the slot's own LCG chain seeded x + y * width.  A ray takes
+ * four draws (the camera ray's) and nothing else advances the chain: sample k uses draws 4k..4k+3.  Sample 0 is
+ * therefore the beauty render's first camera ray; LATER SAMPLES ARE NOT the render's later camera rays, because
+ * the render's chain also holds the draws of each path.  Each ray is traced closest-hit with the context's
+ * ordinary trace.  A hit adds to the slot's record of 12 floats
+ *     (ar, ag, ab, hits,  nx, ny, nz, t,  px, py, pz, 0)
+ * 1 to hits, the hit distance to t, the point p = lerp3(v0, v1, v2, u, v), the geometric normal
+ * normalize(cross(v1 - v0, v2 - v0)) negated when its dot with the ray direction is > 0 (turned towards the
+ * viewer: windings are arbitrary), and the albedo: the colour (at the interpolated texcoord) of the material
+ * the path tracer would shade, found by walking Mix as Material::select_material does with the next draw of a
+ * COPY of the chain after the camera ray as the selector (so the mean over samples is the blend).  Diffuse,
+ * Glossy and Emissive give their colour (Emissive whichever way it faces, so that the filter's albedo stop keeps
+ * a lamp from bleeding into a coplanar ceiling); a null material is a hit with albedo 0.  A miss adds nothing.
+ * All f32, sums in sample order.  spp >= 1; flags: AKR_PT_EXACT_CULL or 0.
+ * The pass keeps the render session (it has its own accumulators and chain states). */
+typedef struct akr_feature_params {
+    int32_t spp;
+    int32_t flags;
+} akr_feature_params;
+/* Host form: ADDS the records into a full-frame features[W*H*12], as akr_hip_render adds its film.  Synchronous. */
+int akr_hip_render_features(akr_hip_ctx *ctx, const akr_feature_params *params, const akr_rect *tiles,
+                            int32_t n_tiles, float *features);
+/* Device form: overwrites a packed d_features[n*12] (slot order) on `stream`; returns n in *n_pixels. */
+int akr_hip_render_features_device(akr_hip_ctx *ctx, const akr_feature_params *params, const akr_rect *tiles,
+                                   int32_t n_tiles, float *d_features, void *stream, uint64_t *n_pixels);
+
+/* Filter.  Inputs, frame ordered: radiance[W*H*3] and weight[W*H] (the film as akr_hip_render returns it: weight 0
+ * outside the tiles, differing weights in an adaptive film) and features[W*H*12] (sums, as above).  Output
+ * out_rgb[W*H*3]: the filtered MEAN colour.  Needs no scene; keeps the session.  Refused with a message: a null
+ * pointer, W * H == 0, parameters out of range.
+ *
+ * Definition (only + - * /, sqrt, fabs, comparisons and rmax / dot / sub / length of akr_math.h; f32, unfused,
+ * left to right).  Per pixel p:
+ *     valid = weight > 0;  c = valid ? radiance / weight : 0
+ *     h = hits;  a, n, t, x = h > 0 ? the record's sums / h : 0;  l = length(n);  nh = l > 0 ? n / l : 0
+ *     per channel m = (demodulate && a.ch > 1e-3f) ? a.ch : 1;  I0 = c / m
+ * Iteration i = 0 .. iterations - 1: step s = 1 << i, sc = sigma_color * (1.0f / (1 << i)),
+ * hk = {1/16, 1/4, 3/8, 1/4, 1/16}; num = den = 0; for j = 0..4 (outer), k = 0..4 (inner) the tap is
+ * q = (x + (k - 2) s, y + (j - 2) s).  A tap is SKIPPED (a select, not a multiply by 0) when q is outside the
+ * frame, q is invalid (its weight is not > 0), or any channel of I_q is not finite.  Tap weight
+ *     w = ((hk[j] * hk[k]) * g) * wc
+ * with g = wc = 1 at the centre tap, and elsewhere
+ *     g  = wn * wz * wa when both p and q have hits, 1 when neither has, 0 otherwise
+ *     wn = rmax(dot(nh_p, nh_q), 0), squared normal_squarings times
+ *     wz = rmax(1 - fabsf(dot(nh_p, sub(x_q, x_p))) / (sigma_depth * t_p), 0)
+ *     wa = rmax(1 - (|da.r| + |da.g| + |da.b|) / sigma_albedo, 0),  da = a_q - a_p
+ *     wc = sigma_color > 0 ? 1 / (1 + dot(d, d) / (sc * sc)) : 1,  d = I_q - I_p
+ * An accepted tap does num += w * I_q per channel and den += w.  The iteration's result: 0 for an invalid p,
+ * I_p unchanged when it is not finite, else den > 0 ? num / den : I_p.
+ * Output: out = I_last * m; invalid pixels give 0. */
+#define AKR_DENOISE_NO_DEMODULATE 1  /* m = 1: films that are not albedo times lighting (ambient occlusion) */
+typedef struct akr_denoise_params {
+    int32_t iterations;        /* 1..8 */
+    int32_t normal_squarings;  /* 0..8 */
+    float sigma_depth;         /* > 0 */
+    float sigma_albedo;        /* > 0 */
+    float sigma_color;         /* <= 0 disables the colour stop */
+    int32_t flags;             /* AKR_DENOISE_NO_DEMODULATE or 0 */
+    int32_t _pad[2];
+} akr_denoise_params;
+/* Host form: host pointers.  Synchronous. */
+int akr_hip_denoise(akr_hip_ctx *ctx, const akr_denoise_params *params, int32_t width, int32_t height,
+                    const float *radiance, const float *weight, const float *features, float *out_rgb);
+/* Device form: device pointers; the work is enqueued on `stream`. */
+int akr_hip_denoise_device(akr_hip_ctx *ctx, const akr_denoise_params *params, int32_t width, int32_t height,
+                           const float *d_radiance, const float *d_weight, const float *d_features,
+                           float *d_out_rgb, void *stream);
 
 /* Host-only BVH build (no device needed): the same builder akr_hip_build_accel runs, for tools
  * and CPU-side checks.  Arrays are owned by the handle; free with akr_bvh_host_free. */
