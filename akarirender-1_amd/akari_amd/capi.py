@@ -125,6 +125,10 @@ class DenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("sigma_color", C.c_float), ("flags", C.c_int32), ("_pad", C.c_int32 * 2)]
 
 
+class DenoiseGuidedParams(C.Structure):
+    _fields_ = [("base", DenoiseParams), ("sigma_variance", C.c_float), ("_pad", C.c_int32 * 3)]
+
+
 FEATURE_FLOATS = 12   # per pixel: albedo rgb, hits, normal xyz, t, position xyz, 0 (sums over the feature samples)
 DENOISE_NO_DEMODULATE = 1
 STRIP = 64   # slots per strip of the adaptive convergence test (packed tile order)
@@ -222,6 +226,11 @@ EXPORTS = {
                                                  C.POINTER(C.c_uint64)]),
     "akr_hip_denoise": (C.c_int, [_P, C.POINTER(DenoiseParams), C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "akr_hip_denoise_device": (C.c_int, [_P, C.POINTER(DenoiseParams), C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "akr_hip_render_variance": (C.c_int, [_P, _P]),
+    "akr_hip_render_variance_device": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64)]),
+    "akr_hip_denoise_guided": (C.c_int, [_P, C.POINTER(DenoiseGuidedParams), C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "akr_hip_denoise_guided_device": (C.c_int, [_P, C.POINTER(DenoiseGuidedParams), C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                                _P, _P]),
 }
 
 _lib = None
@@ -691,6 +700,52 @@ class HipContext:
         self._check(self.lib.akr_hip_denoise_device(self.h, C.byref(p), int(width), int(height), C.c_void_p(d_radiance),
                                                     C.c_void_p(d_weight), C.c_void_p(d_features),
                                                     C.c_void_p(d_out_rgb), C.c_void_p(stream)))
+
+    # ---- film variance from the session's passes and the variance-guided filter
+
+    def render_variance(self, width, height, variance=None):
+        """The session's tracker (option "film_variance" set before the session started), added into a
+        full-frame [H, W, 4] array: per pixel the variance of the mean colour (r, g, b) estimated from the
+        session's batches, and the number of batches K (the variance is 0 while K < 2)."""
+        if variance is None:
+            variance = np.zeros((height, width, 4), np.float32)
+        assert variance.dtype == np.float32 and variance.flags.c_contiguous and variance.size == 4 * width * height
+        self._check(self.lib.akr_hip_render_variance(self.h, _ptr(variance)))
+        return variance
+
+    def render_variance_device(self, d_variance: int, stream: int = 0):
+        """Device form: packed records (4 floats per slot, tile order) overwrite `d_variance`; returns the
+        slot count."""
+        npx = C.c_uint64(0)
+        self._check(self.lib.akr_hip_render_variance_device(self.h, C.c_void_p(d_variance), C.c_void_p(stream),
+                                                            C.byref(npx)))
+        return npx.value
+
+    def denoise_guided(self, radiance, weight, features, variance, **params):
+        """The variance-guided a-trous filter (akr_hip_denoise_guided): denoise() with the frame-ordered
+        variance [H, W, 4] of render_variance.  params: akari_amd.denoise.guided_params()."""
+        from . import denoise as dn
+        p = dn.guided_params(**params)   # refused before the device is touched
+        radiance = np.ascontiguousarray(radiance, np.float32)
+        weight = np.ascontiguousarray(weight, np.float32)
+        features = np.ascontiguousarray(features, np.float32)
+        variance = np.ascontiguousarray(variance, np.float32)
+        dn.check_shapes(radiance, weight, features)
+        dn.check_variance_shape(weight, variance)
+        h, w = weight.shape
+        out = np.zeros((h, w, 3), np.float32)
+        self._check(self.lib.akr_hip_denoise_guided(self.h, C.byref(p), w, h, _ptr(radiance), _ptr(weight),
+                                                    _ptr(features), _ptr(variance), _ptr(out)))
+        return out
+
+    def denoise_guided_device(self, width, height, d_radiance: int, d_weight: int, d_features: int, d_variance: int,
+                              d_out_rgb: int, stream: int = 0, **params):
+        """Device form: frame-ordered device pointers, enqueued on `stream`."""
+        from . import denoise as dn
+        p = dn.guided_params(**params)
+        self._check(self.lib.akr_hip_denoise_guided_device(
+            self.h, C.byref(p), int(width), int(height), C.c_void_p(d_radiance), C.c_void_p(d_weight),
+            C.c_void_p(d_features), C.c_void_p(d_variance), C.c_void_p(d_out_rgb), C.c_void_p(stream)))
 
     def ray_steps(self, n: int) -> np.ndarray:
         """Per-ray traversal iterations of the last standalone trace (option "ray_steps")."""

@@ -23,6 +23,10 @@ With any of the lines above, --denoise writes the film filtered by the edge-avoi
  as the output, previews included: the feature pass (albedo, normal, depth; N camera
 samples per pixel, default 2) runs once per run, the filter once per written film.  --aov writes
 PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm, with or without --denoise.
+       ... --denoise --denoise-variance   with --pass-spp, --preview or --adaptive
+The session tracks the variance of every pixel's mean from its passes and each film is
+filtered by the variance-guided filter, whose colour stop follows how converged a pixel is.  One call is one
+batch, so the render has to run in passes; --aov then also writes PREFIX.variance.pfm.
 """
 from __future__ import annotations
 
@@ -50,15 +54,22 @@ class FilmPost:
     [H, W, 3] (None without --denoise), `features` the feature sums [H, W, 12]."""
 
     def __init__(self, do_denoise: bool, iterations: Optional[int] = None, feature_spp: Optional[int] = None,
-                 per_pass: bool = False):
+                 per_pass: bool = False, guided: bool = False):
         self.do_denoise = bool(do_denoise)
+        self.guided = bool(guided)   # --denoise-variance: the session tracks the variance, the guided filter runs
         self.params = {} if iterations is None else {"iterations": int(iterations)}
-        denoise.params(**self.params)   # refused here, before a device is touched
+        (denoise.guided_params if self.guided else denoise.params)(**self.params)   # refused here, before a device is touched
+        self.variance = None   # with `guided`: [H, W, 4] of the last film handed to finish()
         self.feature_spp = denoise.DEFAULT_FEATURE_SPP if feature_spp is None else int(feature_spp)
         if self.feature_spp < 1:
             raise ValueError("the feature pass needs at least one sample")
         self.per_pass = bool(per_pass) and self.do_denoise
         self.features = self.image = self._film = None
+
+    def start(self, ctx: "capi.HipContext") -> None:
+        """Before the first render of the run: the session's variance tracker is an option read when it starts."""
+        if self.guided:
+            ctx.set_option("film_variance", 1)
 
     def bind(self, tiles, width: int, height: int, demodulate: bool = True) -> None:
         """The run's tile list and frame; demodulate=False for films that are not albedo times lighting (AO)."""
@@ -71,7 +82,11 @@ class FilmPost:
             return
         if self.features is None:
             self.features = ctx.render_features(self.feature_spp, self.tiles, self.width, self.height)
-        if self.do_denoise:
+        if self.guided:
+            self.variance = ctx.render_variance(self.width, self.height)
+        if self.do_denoise and self.guided:
+            self.image = ctx.denoise_guided(radiance, weight, self.features, self.variance, **self.params)
+        elif self.do_denoise:
             self.image = ctx.denoise(radiance, weight, self.features, **self.params)
         self._film = radiance
 
@@ -81,6 +96,8 @@ class FilmPost:
         film.write_pfm(prefix + ".albedo.pfm", albedo, one)
         film.write_pfm(prefix + ".normal.pfm", normal, one)
         film.write_pfm(prefix + ".depth.pfm", np.repeat(depth[..., None], 3, axis=-1), one)
+        if self.variance is not None:   # the variance of each pixel's mean colour (0 where it has fewer than two batches)
+            film.write_pfm(prefix + ".variance.pfm", np.ascontiguousarray(self.variance[..., :3]), one)
 
 
 def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[FilmPost] = None,
@@ -141,11 +158,11 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
             raise progressive.CheckpointError(f"checkpoint holds {ck.spp_done} spp, more than the {it.spp} asked for")
     with capi.HipContext(device) as ctx:
         scene.upload_scene(ctx, cs, **build_kw)
+        if post is not None:
+            post.start(ctx)   # before the restore: an imported film is the tracker's first batch
+            post.bind(tiles, w, h)
         if ck is not None:
             ck.restore(ctx, cs, tiles)
-
-        if post is not None:
-            post.bind(tiles, w, h)
 
         def each_pass(done, rad, wt):
             if checkpoint is not None:
@@ -179,6 +196,7 @@ def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, mi
         tiles = _tiles(sc, it.tile_size)
         each = on_pass
         if post is not None:
+            post.start(ctx)
             post.bind(tiles, w, h)
             if on_pass is not None and post.per_pass:
                 def each(info, rad, wt):
@@ -235,7 +253,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     help=f"with --denoise or --aov: camera samples per pixel of the feature pass "
                          f"(default {denoise.DEFAULT_FEATURE_SPP})")
     ap.add_argument("--aov", default=None, metavar="PREFIX",
-                    help="write PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm")
+                    help="write PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm "
+                         "(and PREFIX.variance.pfm with --denoise-variance)")
+    ap.add_argument("--denoise-variance", action="store_true",
+                    help="with --denoise and one of --pass-spp, --preview, --adaptive: track each pixel's variance "
+                         "from the passes and filter with the variance-guided filter")
     args = ap.parse_args(argv)
     if args.denoise_iters is not None:  # refused before the scene is read
         if not args.denoise:
@@ -249,9 +271,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ap.error("--feature-spp needs at least one sample")
     if args.aov is not None and not args.aov:
         ap.error("--aov needs a file prefix")
+    if args.denoise_variance:  # refused before the scene is read
+        if not args.denoise:
+            ap.error("--denoise-variance needs --denoise")
+        if args.pass_spp is None and not args.preview and args.adaptive is None:
+            ap.error("--denoise-variance needs one of --pass-spp, --preview, --adaptive: the variance comes from the "
+                     "spread of the passes, and one call is one batch")
+        if args.gpus != 1:
+            ap.error("--denoise-variance renders on one GPU (--gpus 1)")
     post = None
     if args.denoise or args.aov is not None:
-        post = FilmPost(args.denoise, args.denoise_iters, args.feature_spp, per_pass=args.preview)
+        post = FilmPost(args.denoise, args.denoise_iters, args.feature_spp, per_pass=args.preview,
+                        guided=args.denoise_variance)
     if args.adaptive is not None:  # refused before the scene is read
         if args.checkpoint is not None or args.resume is not None:
             ap.error("--adaptive cannot be combined with --checkpoint or --resume: a checkpoint holds a film "

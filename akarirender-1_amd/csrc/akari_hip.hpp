@@ -349,6 +349,31 @@ class HipPathTracer {
               "denoise");
     }
 
+    // Film variance from the session's passes and the variance-guided filter (include/akr_hip.h, DESIGN.md
+    // §3.16).  track_variance before the render that starts the session; render_variance: `variance` is
+    // cleared and then holds (vr, vg, vb, K) per pixel, the variance of the mean colour and the batch count.
+    void track_variance(const HipAccelerator &scene, bool on = true) const {
+        check(scene.handle(), akr_hip_set_option(scene.handle(), "film_variance", on ? 1 : 0), "track_variance");
+    }
+    void render_variance(const HipAccelerator &scene, const Film &film, std::vector<float> &variance) const {
+        variance.assign(4 * (size_t)film.width * film.height, 0.0f);
+        check(scene.handle(), akr_hip_render_variance(scene.handle(), variance.data()), "render_variance");
+    }
+    static akr_denoise_guided_params denoise_guided_defaults() {
+        return akr_denoise_guided_params{denoise_defaults(), 2.0f, {0, 0, 0}};
+    }
+    void denoise_guided(const HipAccelerator &scene, const Film &film, const std::vector<float> &features,
+                        const std::vector<float> &variance, std::vector<float> &out_rgb,
+                        const akr_denoise_guided_params &p = denoise_guided_defaults()) const {
+        if (features.size() != 12 * film.weight.size()) throw std::runtime_error("denoise: twelve feature sums per pixel");
+        if (variance.size() != 4 * film.weight.size()) throw std::runtime_error("denoise: four variance floats per pixel");
+        out_rgb.assign(film.radiance.size(), 0.0f);
+        check(scene.handle(),
+              akr_hip_denoise_guided(scene.handle(), &p, film.width, film.height, film.radiance.data(), film.weight.data(),
+                                     features.data(), variance.data(), out_rgb.data()),
+              "denoise_guided");
+    }
+
     // Multi-GPU in one process (akr_hip_render_node): tile j on accelerators[j % n], one per device,
     // each built from the same scene; the merged film equals render() on one of them.
     void render_node(const std::vector<const HipAccelerator *> &accels, Film &film) const {

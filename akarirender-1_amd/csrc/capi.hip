@@ -272,6 +272,46 @@ struct akr_hip_ctx {
     DBuf<uint8_t> d_mask, d_scan_tmp, d_strip_active;
     DBuf<float> d_strip_err;
     DBuf<float4> d_prev;
+    // Film variance tracker, for sessions started with option "film_variance": each slot's
+    // film at its last update and (M2r, M2g, M2b, K), sized with the session; var_track is the option as the
+    // session's first call read it.  d_var_out stages an export.
+    DBuf<float4> d_var_prev, d_var_m2;
+    DBuf<float> d_var_out;
+    bool var_track = false;
+    // A session starts: the tracker's state is zeroed (nothing is allocated or enqueued with the option off)
+    void variance_begin(uint64_t N, hipStream_t st) {
+        var_track = opt.film_variance;
+        if (!var_track || N == 0) return;
+        d_var_prev.reserve(N);
+        d_var_m2.reserve(N);
+        HIPCHK(hipMemsetAsync(d_var_prev.p, 0, N * sizeof(float4), st));
+        HIPCHK(hipMemsetAsync(d_var_m2.p, 0, N * sizeof(float4), st));
+    }
+    // After the last kernel that writes d_film has been joined into `st`: one batch for every slot whose
+    // weight grew
+    void variance_update(uint64_t N, hipStream_t st) {
+        if (!var_track || N == 0) return;
+        if (d_var_prev.n < N || d_var_m2.n < N) throw std::runtime_error("film variance: the tracker's buffers changed");
+        timed("variance_update", st, [&] { launch_variance_update(d_film.p, (uint32_t)N, d_var_prev.p, d_var_m2.p, st); });
+        HIPCHK(hipGetLastError());
+    }
+    // (vr, vg, vb, K) of every slot into `out` (device, packed) on `st`; returns the slots
+    uint64_t require_variance() const {
+        const uint64_t N = require_session().n;
+        if (!var_track)
+            throw std::runtime_error("film variance: the session was started without option film_variance "
+                                     "(set it to 1 before the render or import that starts the session)");
+        return N;
+    }
+    uint64_t variance_resolve(float *out, hipStream_t st) {
+        const uint64_t N = require_variance();
+        serialize(st);
+        if (N == 0) return 0;
+        if (d_var_prev.n < N || d_var_m2.n < N) throw std::runtime_error("film variance: the tracker's buffers changed");
+        timed("variance_resolve", st, [&] { launch_variance_resolve(d_film.p, d_var_m2.p, (uint32_t)N, out, st); });
+        HIPCHK(hipGetLastError());
+        return N;
+    }
     std::vector<uint32_t> h_pixel;
     bool h_pixel_ok = false;
     DBuf<uint32_t> d_pixel, d_seed, d_slot0, d_slot1, d_counts;
@@ -1067,6 +1107,7 @@ struct akr_hip_ctx {
         probe_n = 0;
         const bool resume = cont && require_session().seeded;  // else every slot starts from x + y * width
         const uint64_t N = cont ? resume_pixels(n_count_words, st) : setup_pixels(tiles, n_tiles, n_count_words, st);
+        if (!cont) variance_begin(N, st);  // zeroed on st beside the render; the update follows the join below
         if (N == 0) return 0;
         if (subset && (!cont || n_subset == 0 || n_subset > N)) throw std::runtime_error("render: invalid slot subset");
         const uint64_t M = subset ? n_subset : N;  // the slots this pass fetches
@@ -1100,6 +1141,7 @@ struct akr_hip_ctx {
             render_wavefront(pass);
         }
         join_streams(st);
+        if (p.spp > 0) variance_update(N, st);
         return N;
     }
 
@@ -1504,6 +1546,56 @@ struct akr_hip_ctx {
             const float sc = p.sigma_color * (1.0f / (float)(1 << i));
             a.sc2 = sc * sc;
             timed("denoise", st, [&] { launch_denoise_atrous(a, st); });
+        }
+        timed("denoise_finish", st, [&] { launch_denoise_finish(d_dn_guide.p, d_dn_I[p.iterations & 1].p, n, dm, out, st); });
+        HIPCHK(hipGetLastError());
+        mark_done(st);
+    }
+
+    // ---- the variance-guided filter
+    DBuf<float4> d_dn_V[2];
+
+    static void check_denoise_guided(const akr_denoise_guided_params *p, int32_t width, int32_t height) {
+        if (!p) throw std::runtime_error("denoise: null parameters");
+        check_denoise(&p->base, width, height);
+        if (!(p->sigma_variance > 0.0f) || !std::isfinite(p->sigma_variance))
+            throw std::runtime_error("denoise: sigma_variance must be > 0 and finite");
+    }
+
+    // denoise() with the frame-ordered variance (vr, vg, vb, K): the same prep and finish, the guided iteration
+    void denoise_guided(const akr_denoise_guided_params &gp, int32_t width, int32_t height, const float *rad, const float *w,
+                        const float *feat, const float *var, float *out, hipStream_t st) {
+        const akr_denoise_params &p = gp.base;
+        const uint32_t n = (uint32_t)((uint64_t)width * (uint64_t)height);
+        d_dn_guide.reserve(3 * (size_t)n);
+        for (int k = 0; k < 2; k++) {
+            d_dn_I[k].reserve(n);
+            d_dn_V[k].reserve(n);
+        }
+        const bool dm = !(p.flags & AKR_DENOISE_NO_DEMODULATE);
+        serialize(st);
+        timed("denoise_prep", st, [&] { launch_denoise_prep(rad, w, feat, n, dm, d_dn_guide.p, d_dn_I[0].p, st); });
+        timed("denoise_prep_variance", st,
+              [&] { launch_denoise_prep_variance(var, d_dn_guide.p, d_dn_I[0].p, n, dm, d_dn_V[0].p, st); });
+        for (int i = 0; i < p.iterations; i++) {
+            DenoiseGuidedArgs g{};
+            DenoiseArgs &a = g.d;
+            a.guide = d_dn_guide.p;
+            a.in = d_dn_I[i & 1].p;
+            a.out = d_dn_I[(i + 1) & 1].p;
+            a.width = width;
+            a.height = height;
+            a.step = 1 << i;
+            a.squarings = p.normal_squarings;
+            a.color_stop = p.sigma_color > 0.0f ? 1 : 0;
+            a.sigma_depth = p.sigma_depth;
+            a.sigma_albedo = p.sigma_albedo;
+            const float sc = p.sigma_color * (1.0f / (float)(1 << i));
+            a.sc2 = sc * sc;
+            g.vin = d_dn_V[i & 1].p;
+            g.vout = d_dn_V[(i + 1) & 1].p;
+            g.sv3 = (3.0f * gp.sigma_variance) * gp.sigma_variance;
+            timed("denoise_guided", st, [&] { launch_denoise_atrous_guided(g, st); });
         }
         timed("denoise_finish", st, [&] { launch_denoise_finish(d_dn_guide.p, d_dn_I[p.iterations & 1].p, n, dm, out, st); });
         HIPCHK(hipGetLastError());
@@ -2145,6 +2237,73 @@ int akr_hip_denoise_device(akr_hip_ctx *ctx, const akr_denoise_params *params, i
     });
 }
 
+int akr_hip_denoise_guided(akr_hip_ctx *ctx, const akr_denoise_guided_params *params, int32_t width, int32_t height,
+                           const float *radiance, const float *weight, const float *features, const float *variance,
+                           float *out_rgb) {
+    return guard(ctx, [&] {
+        if (!radiance || !weight || !features || !variance || !out_rgb) throw std::runtime_error("denoise: null argument");
+        akr_hip_ctx::check_denoise_guided(params, width, height);
+        const size_t n = (size_t)width * (size_t)height;
+        hipStream_t st = ctx->stream;
+        ctx->serialize(st);  // the staging buffers are shared by every denoise of the context
+        ctx->d_dn_in.reserve(20 * n);
+        ctx->d_dn_out.reserve(3 * n);
+        float *d_rad = ctx->d_dn_in.p, *d_w = d_rad + 3 * n, *d_feat = d_rad + 4 * n, *d_var = d_rad + 16 * n;
+        HIPCHK(hipMemcpyAsync(d_rad, radiance, 3 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_w, weight, n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_feat, features, 12 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_var, variance, 4 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        ctx->denoise_guided(*params, width, height, d_rad, d_w, d_feat, d_var, ctx->d_dn_out.p, st);
+        HIPCHK(hipMemcpyAsync(out_rgb, ctx->d_dn_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
+        ctx->mark_done(st);
+        HIPCHK(hipStreamSynchronize(st));
+    });
+}
+
+int akr_hip_denoise_guided_device(akr_hip_ctx *ctx, const akr_denoise_guided_params *params, int32_t width, int32_t height,
+                                  const float *d_radiance, const float *d_weight, const float *d_features,
+                                  const float *d_variance, float *d_out_rgb, void *stream) {
+    return guard(ctx, [&] {
+        if (!d_radiance || !d_weight || !d_features || !d_variance || !d_out_rgb)
+            throw std::runtime_error("denoise: null argument");
+        akr_hip_ctx::check_denoise_guided(params, width, height);
+        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        ctx->denoise_guided(*params, width, height, d_radiance, d_weight, d_features, d_variance, d_out_rgb, st);
+    });
+}
+
+int akr_hip_render_variance(akr_hip_ctx *ctx, float *variance) {
+    return guard(ctx, [&] {
+        if (!variance) throw std::runtime_error("null argument");
+        hipStream_t st = ctx->stream;
+        const uint64_t n = ctx->require_variance();
+        ctx->serialize(st);  // the staging buffer is shared by every export of the context
+        ctx->d_var_out.reserve(4 * n);
+        const uint64_t N = ctx->variance_resolve(ctx->d_var_out.p, st);
+        if (N == 0) return;
+        std::vector<float> rec(4 * N);
+        HIPCHK(hipMemcpyAsync(rec.data(), ctx->d_var_out.p, rec.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        ctx->mark_done(st);
+        HIPCHK(hipStreamSynchronize(st));
+        const int W = ctx->cam.width;
+        const std::vector<uint32_t> &pl = ctx->host_pixels();
+        for (uint64_t k = 0; k < N; k++) {
+            const uint64_t pix = (uint64_t)(pl[k] & 0xFFFFu) + (uint64_t)(pl[k] >> 16) * W;
+            for (int c = 0; c < 4; c++) variance[4 * pix + c] += rec[4 * k + c];
+        }
+    });
+}
+
+int akr_hip_render_variance_device(akr_hip_ctx *ctx, float *d_variance, void *stream, uint64_t *n_pixels) {
+    return guard(ctx, [&] {
+        if (!d_variance) throw std::runtime_error("null argument");
+        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        const uint64_t N = ctx->variance_resolve(d_variance, st);
+        if (n_pixels) *n_pixels = N;
+        ctx->mark_done(st);
+    });
+}
+
 int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_rect *tiles, int32_t n_tiles,
                           float *d_radiance, float *d_weight, void *stream, uint64_t *n_pixels) {
     return guard(ctx, [&] {
@@ -2579,6 +2738,9 @@ int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, c
             HIPCHK(hipMemcpyAsync(ctx->d_seed.p, sampler, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(ctx->d_film.p, film, N * sizeof(float4), hipMemcpyHostToDevice, st));
         }
+        // the tracker takes the imported film as one batch: P = the film, K = 1 where the weight is positive
+        ctx->variance_begin(N, st);
+        ctx->variance_update(N, st);
         ctx->mark_done(st);
         HIPCHK(hipStreamSynchronize(st));  // the caller's arrays are free again
         ctx->probe_ok = false;

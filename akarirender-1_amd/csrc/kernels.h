@@ -80,4 +80,19 @@ void launch_denoise_atrous(const DenoiseArgs &a, hipStream_t st);
 void launch_denoise_finish(const float4 *guide, const float4 *I, uint32_t n, bool demodulate, float *out_rgb,
                            hipStream_t st);
 
+// the variance-guided filter: DenoiseArgs with a ping-pong pair of its own for the variance
+// record V = (variance of the demodulated mean | hv as 1 or 0)
+struct DenoiseGuidedArgs {
+    DenoiseArgs d;
+    const float4 *vin;
+    float4 *vout;
+    float sv3;  // (3 * sigma_variance) * sigma_variance
+};
+void launch_denoise_prep_variance(const float *variance, const float4 *guide, const float4 *I, uint32_t n, bool demodulate,
+                                  float4 *V, hipStream_t st);
+void launch_denoise_atrous_guided(const DenoiseGuidedArgs &a, hipStream_t st);
+// the film variance tracker: P = each slot's film at its last update, M = (M2r, M2g, M2b, K)
+void launch_variance_update(const float4 *film, uint32_t n, float4 *P, float4 *M, hipStream_t st);
+void launch_variance_resolve(const float4 *film, const float4 *M, uint32_t n, float *out, hipStream_t st);
+
 }  // namespace akr

@@ -18,6 +18,10 @@ struct Options {
     bool probe() const { return pixel_probe != 0; }
     bool probe_clock() const { return pixel_probe == 2; }
     bool fault_test = false;  // option "fault_test": k_path_defer raises the fault word once (tests)
+    // option "film_variance" (default 0, read when a session starts): the session tracks the variance of every
+    // slot's mean from its passes (k_variance_update after each call that draws samples).
+    // Off: nothing is allocated or launched
+    bool film_variance = false;
 
     // The render form of a constant-shading scene.  A "tail form"
     // (k_path_spec, or k_path_defer when path_spec is 0) pays where k_path's launch would end on a few
@@ -236,6 +240,13 @@ inline int64_t get_option(const Options &o, const OptionRow &r) { return r.b ? (
 
 // Stores `value` under `key`.  Returns an empty string, or why the value was refused (`o` is then unchanged).
 inline std::string set_option(Options &o, const char *key, int64_t value) {
+    // a session switch, not a knob of the render: kOptionTable stays the record of the knobs row for row
+    // (tests/golden/options.json), and this one name is matched before it
+    if (key && strcmp(key, "film_variance") == 0) {
+        if (value != 0 && value != 1) return "film_variance must be in [0, 1]";
+        o.film_variance = value == 1;
+        return {};
+    }
     const OptionRow *r = find_option(key);
     if (!r) return "unknown option '" + std::string(key ? key : "") + "'";
     const bool pow2 = r->kind == OptionRow::POW2;

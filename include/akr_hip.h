@@ -228,6 +228,9 @@ const char *akr_hip_last_error(const akr_hip_ctx *ctx);
  * akr_pixel_probe per slot), "fault_test" (raise the hang guard's fault word once), "ray_steps",
  * "serial_shadow", "any_far_first". */
 int akr_hip_set_option(akr_hip_ctx *ctx, const char *key, int64_t value);
+/* One more key is a session switch rather than a knob of the render: "film_variance" (0 or 1, default 0; read when a
+ * session starts) makes the session track the variance of every slot's mean from its passes, see
+ * akr_hip_render_variance below. */
 
 int akr_hip_upload_mesh(akr_hip_ctx *ctx, const float *vertices, uint64_t n_vertices,
                         const int32_t *indices, const float *normals, const float *texcoords,
@@ -309,6 +312,11 @@ int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const a
  *  - akr_hip_trace, akr_hip_trace_device and the query calls keep it.
  *  - akr_hip_render_features, akr_hip_render_features_device, akr_hip_denoise and akr_hip_denoise_device keep
  *    it: they touch neither the film, the sampler states, the per-slot counts nor the session record.
+ *    So do akr_hip_render_variance, akr_hip_render_variance_device, akr_hip_denoise_guided and its device form.
+ *  - With option "film_variance" set when the session starts, the session also tracks the variance of every
+ *    slot's mean from its passes: a fresh render starts the tracker from nothing, an import takes the imported
+ *    film as one batch, every continue adds a batch, and whatever ends the session ends the tracker (the rules
+ *    are with akr_hip_render_variance below).  The film, the sampler states and the probe do not depend on it.
  *  - akr_hip_set_option between segments is allowed, and may switch the render form, the cost order
  *    and exact_cull: all give the same bits.
  *  - spp = 0 renders nothing and returns the totals.  A total above 2^24 samples per slot is refused
@@ -493,6 +501,71 @@ int akr_hip_denoise(akr_hip_ctx *ctx, const akr_denoise_params *params, int32_t 
 int akr_hip_denoise_device(akr_hip_ctx *ctx, const akr_denoise_params *params, int32_t width, int32_t height,
                            const float *d_radiance, const float *d_weight, const float *d_features,
                            float *d_out_rgb, void *stream);
+
+/* ---- Film variance from the session's passes, and the variance-guided filter.
+ *
+ * Tracker.  Option "film_variance" (0 / 1, default 0) is read when a session starts.  With it on, the session
+ * carries per slot a snapshot P of the film at the slot's last update and (M2r, M2g, M2b, K), K the number of
+ * batches as an f32 count.  After every call that draws samples (the fresh render, akr_hip_render_continue,
+ * akr_hip_render_continue_masked, every pass of akr_hip_render_adaptive, akr_hip_adaptive_begin / _step, and the
+ * device forms of these) each slot is updated from the film F = (R, G, B, W); f32, unfused, left to right,
+ * correctly rounded /:
+ *     n = F.w - P.w;  if !(n > 0) the slot stays as it is
+ *     if P.w > 0:  per channel  d = (F.ch - P.ch) / n - P.ch / P.w
+ *                               M2.ch = M2.ch + (d * d) * ((P.w * n) / F.w)
+ *     K = K + 1;  P = F
+ * (West's weighted incremental update on the batch means: a slot's first batch leaves M2 at 0 and K at 1, and
+ * M2 / (K - 1) estimates the per-sample variance without bias whatever the batch sizes.)  A call that draws no
+ * sample updates nothing; with the option off nothing is allocated or launched.
+ *  - A fresh render starts from P = 0, M2 = 0, K = 0.
+ *  - akr_hip_render_state_import sets P to the imported film and K to 1 where the weight is positive: a
+ *    checkpoint is ONE batch, whatever passes rendered it (a checkpoint holds no variance).
+ *  - The tracker has its own snapshot; it does not use the adaptive render's.
+ *  - akr_hip_render_features, akr_hip_denoise, akr_hip_denoise_guided, traces and queries keep the tracker;
+ *    whatever ends the session ends it.
+ *  - Masked and adaptive sessions need nothing special: a slot's weight is its count, and a slot a pass leaves
+ *    out sees n = 0.
+ * Export: per slot (vr, vg, vb, K); for K >= 2  v.ch = (M2.ch / (K - 1)) / F.w, the variance of the slot's MEAN
+ * colour, else 0.  The host form ADDS the records into a full-frame variance[W*H*4], as akr_hip_render adds its
+ * film (pass a zeroed buffer; K adds up where tiles overlap).  The device form overwrites a packed
+ * d_variance[n*4] (slot order) on `stream` and returns n in *n_pixels.  Both keep the session.  Both are refused
+ * with a message that says why when the context has no session ("no render session ...") or the session was
+ * started without "film_variance" ("film variance: the session was started without option film_variance"). */
+int akr_hip_render_variance(akr_hip_ctx *ctx, float *variance);
+int akr_hip_render_variance_device(akr_hip_ctx *ctx, float *d_variance, void *stream, uint64_t *n_pixels);
+
+/* Guided filter: akr_hip_denoise with one more frame-ordered input variance[W*H*4] (as above: the variance of the
+ * mean colour and K) and sigma_variance (> 0 and finite).  akr_hip_denoise and its struct are unchanged.
+ *
+ * Definition: that of akr_hip_denoise with these additions (f32, unfused, left to right, the same operations).
+ * Per pixel p, with valid and the demodulation divisor m of akr_hip_denoise:
+ *     hv = valid && K >= 2 && vr, vg, vb finite;  V0.ch = hv ? v.ch / (m.ch * m.ch) : 0
+ * hv never changes.  Each iteration, before the taps, for a pixel with hv:
+ *     G = the 3x3 mean of the current V at stride 1: gk = {1/4, 1/2, 1/4}, gn = gd = 0; for j = 0..2 (outer),
+ *     k = 0..2 (inner) the tap q = (x + k - 1, y + j - 1) is SKIPPED when it is outside the frame or has no hv
+ *     (an invalid pixel has none), else gn.ch += (gk[j] * gk[k]) * V_q.ch, gd += gk[j] * gk[k];
+ *     G = gd > 0 ? gn / gd : V_p
+ * Colour stop of a non-centre tap when p has hv (whatever sigma_color is):
+ *     e.ch = (d.ch * d.ch) / (G.ch + 1e-8f),  r = ((e.r + e.g) + e.b) / ((3.0f * sigma_variance) * sigma_variance)
+ *     wc = 1 / (1 + r)
+ * The stride does not tighten it: the propagated variance shrinks by itself.  A pixel without hv keeps the wc of
+ * akr_hip_denoise, sigma_color included.
+ * Propagation: every accepted tap also does vnum.ch += (w * w) * V_q.ch, with V_q = 0 when q has no hv.  The
+ * iteration's V: V_p unchanged for an invalid or non-finite p, else den > 0 ? vnum / (den * den) : V_p.
+ * Unchanged: the skip rules for out-of-frame, invalid and non-finite taps, the result rules for invalid and
+ * non-finite pixels, g, the stencil and the remodulation.  So with no hv pixel anywhere the output equals
+ * akr_hip_denoise's bit for bit. */
+typedef struct akr_denoise_guided_params {
+    akr_denoise_params base;
+    float sigma_variance;      /* > 0 and finite; 2 is the library's default */
+    int32_t _pad[3];
+} akr_denoise_guided_params;
+int akr_hip_denoise_guided(akr_hip_ctx *ctx, const akr_denoise_guided_params *params, int32_t width, int32_t height,
+                           const float *radiance, const float *weight, const float *features, const float *variance,
+                           float *out_rgb);
+int akr_hip_denoise_guided_device(akr_hip_ctx *ctx, const akr_denoise_guided_params *params, int32_t width,
+                                  int32_t height, const float *d_radiance, const float *d_weight,
+                                  const float *d_features, const float *d_variance, float *d_out_rgb, void *stream);
 
 /* Host-only BVH build (no device needed): the same builder akr_hip_build_accel runs, for tools
  * and CPU-side checks.  Arrays are owned by the handle; free with akr_bvh_host_free. */
