@@ -441,7 +441,17 @@ V3 closure_eval(const Closure &c, V3 wo, V3 wi) {
     }
     return v3(0, 0, 0);
 }
-// closure sample (material.h:79-85, 123-137; microfacet sample_wh :125-149)
+// MicrofacetModel::sample_wh, the EGGX case (microfacet.h:125-149)
+V3 ggx_sample_wh(float alpha, V3 wo, V2 u) {
+    float phi = 2 * kPi * u.y;
+    float t2 = alpha * alpha * u.x / (1 - u.x);
+    float cos_t = 1.0f / std::sqrt(1 + t2);
+    float sin_t = std::sqrt(rmax(0.0f, 1 - cos_t * cos_t));
+    V3 wh = v3(fcos(phi) * sin_t, cos_t, fsin(phi) * sin_t);
+    if (!same_hemisphere(wo, wh)) wh = neg(wh);
+    return wh;
+}
+// closure sample (material.h:79-85, 123-137)
 V3 closure_sample(const Closure &c, V2 u, V3 wo, V3 &wi, float &pdf) {
     if (c.kind == 1) {
         wi = cosine_hemisphere(u);
@@ -449,13 +459,7 @@ V3 closure_sample(const Closure &c, V2 u, V3 wo, V3 &wi, float &pdf) {
         pdf = std::abs(wi.y) * kInvPi;
         return muls(c.R, kInvPi);
     }
-    // GGX sample_wh
-    float phi = 2 * kPi * u.y;
-    float t2 = c.alpha * c.alpha * u.x / (1 - u.x);
-    float cos_t = 1.0f / std::sqrt(1 + t2);
-    float sin_t = std::sqrt(rmax(0.0f, 1 - cos_t * cos_t));
-    V3 wh = v3(fcos(phi) * sin_t, cos_t, fsin(phi) * sin_t);
-    if (!same_hemisphere(wo, wh)) wh = neg(wh);
+    V3 wh = ggx_sample_wh(c.alpha, wo, u);
     // reflect: -1 * w + 2 * dot(w, n) * n (bsdf-funcs.h:52-54)
     wi = add(muls(wo, -1.0f), muls(wh, 2.0f * dot(wo, wh)));
     if (!same_hemisphere(wo, wi)) {
@@ -494,6 +498,41 @@ struct Distribution {  // Distribution1D (common/distribution.h:46-102)
         return i;
     }
 };
+
+// Material::select_material (material.h:255-271): walks Mix nodes, rescaling u; returns choice_pdf
+float select_material(const orc_scene &s, const akr_material *&mat, float &sel_u, V2 tc) {
+    float choice_pdf = 1.0f;
+    while (mat->type == AKR_MAT_MIX) {
+        float frac = tex_eval(s, mat->fraction, tc).x;
+        if (sel_u < frac) {
+            sel_u = sel_u / frac;
+            mat = &s.materials[mat->second];
+            choice_pdf *= 1.0f / frac;
+        } else {
+            sel_u = (sel_u - frac) / (1.0f - frac);
+            mat = &s.materials[mat->first];
+            choice_pdf *= 1.0f / (1.0f - frac);
+        }
+    }
+    return choice_pdf;
+}
+
+// AreaLight::sample (light.h:58-71)
+struct LightSample { V3 wi, L; float pdf; Ray shadow; };
+LightSample light_sample(const orc_scene &s, const Tri &lt, V2 lu, V3 p) {
+    float su0 = std::sqrt(lu.x);
+    float b0 = 1 - su0, b1 = lu.y * su0;
+    V3 lp = lerp3(lt.v[0], lt.v[1], lt.v[2], b0, b1);
+    V3 lng = tri_ng(lt);
+    V3 lwi = sub(lp, p);
+    float dist_sqr = dot(lwi, lwi);
+    lwi = divs(lwi, std::sqrt(dist_sqr));
+    V2 ltc = lerp3(lt.tc[0], lt.tc[1], lt.tc[2], b0, b1);
+    V3 Le = tex_eval(s, s.materials[lt.mat].color, ltc);
+    float lpdf = dist_sqr / rmax(0.0f, -dot(lwi, lng)) / tri_area(lt);
+    Ray shadow{lp, neg(lwi), kEps / std::abs(dot(lwi, lng)), std::sqrt(dist_sqr) * (1.0f - kShadowEps)};
+    return {lwi, Le, lpdf, shadow};
+}
 
 struct Scene {
     const orc_scene *s;
@@ -559,19 +598,8 @@ V3 trace_path(const Scene &sc, Lcg &sampler, int x, int y, int max_depth, bool t
         }
         if (depth >= max_depth) break;
         // Material::get_bsdf -> select_material (material.h:251-268) -> get_bsdf0
-        float sel_u = cu1.x, choice_pdf = 1.0f;
-        while (mat->type == AKR_MAT_MIX) {
-            float frac = tex_eval(s, mat->fraction, tc).x;
-            if (sel_u < frac) {
-                sel_u = sel_u / frac;
-                mat = &s.materials[mat->second];
-                choice_pdf *= 1.0f / frac;
-            } else {
-                sel_u = (sel_u - frac) / (1.0f - frac);
-                mat = &s.materials[mat->first];
-                choice_pdf *= 1.0f / (1.0f - frac);
-            }
-        }
+        float sel_u = cu1.x;
+        float choice_pdf = select_material(s, mat, sel_u, tc);
         Closure cl{0, v3(0, 0, 0), 0};
         if (mat->type == AKR_MAT_DIFFUSE) {
             cl.kind = 1;
@@ -605,18 +633,10 @@ V3 trace_path(const Scene &sc, Lcg &sampler, int x, int y, int max_depth, bool t
             if (idx == sc.lights.size()) idx -= 1;
             const Tri &lt = sc.lights[idx];
             V2 lu = sampler.next2d();
-            // AreaLight::sample (light.h:58-71)
-            float su0 = std::sqrt(lu.x);
-            float b0 = 1 - su0, b1 = lu.y * su0;
-            V3 lp = lerp3(lt.v[0], lt.v[1], lt.v[2], b0, b1);
-            V3 lng = tri_ng(lt);
-            V3 lwi = sub(lp, p);
-            float dist_sqr = dot(lwi, lwi);
-            lwi = divs(lwi, std::sqrt(dist_sqr));
-            V2 ltc = lerp3(lt.tc[0], lt.tc[1], lt.tc[2], b0, b1);
-            V3 Le = tex_eval(s, s.materials[lt.mat].color, ltc);
-            float lpdf = dist_sqr / rmax(0.0f, -dot(lwi, lng)) / tri_area(lt);
-            Ray shadow{lp, neg(lwi), kEps / std::abs(dot(lwi, lng)), std::sqrt(dist_sqr) * (1.0f - kShadowEps)};
+            LightSample ls = light_sample(s, lt, lu, p);
+            const V3 lwi = ls.wi, Le = ls.L;
+            const float lpdf = ls.pdf;
+            const Ray shadow = ls.shadow;
             if (!(lpdf <= 0.0f)) {
                 float light_pdf = sel_pdf * lpdf;
                 V3 fe = closure_eval(cl, to_local(frame, wo), to_local(frame, lwi));
@@ -636,6 +656,29 @@ V3 trace_path(const Scene &sc, Lcg &sampler, int x, int y, int max_depth, bool t
         st.ext++;
     }
     return L;
+}
+
+// One pixel of cpu::PathTracer::render's loop (cpu/integrator.cpp:124-135): spp samples from the
+// sampler state seed0, summed as Tile::add_sample does; returns the sampler after the last sample.
+Lcg pixel_samples(const Scene &sc, const akr_pt_params &p, int x, int y, uint32_t seed0, bool tight, PathStats &st,
+                  V3 &acc, float &wsum, PixelTally &pt) {
+    const float clampv = p.ray_clamp;
+    Lcg sampler{seed0};
+    acc = v3(0, 0, 0);
+    wsum = 0;
+    for (int sidx = 0; sidx < p.spp; sidx++) {
+        V3 L = trace_path(sc, sampler, x, y, p.max_depth, tight, st, pt);
+        if (clampv > 0) {  // gpu/cuda/integrator.cpp:397-398 (GPU-only clamp)
+            V3 c;
+            c.x = std::isnan(L.x) ? 0.0f : rmax(0.0f, L.x);
+            c.y = std::isnan(L.y) ? 0.0f : rmax(0.0f, L.y);
+            c.z = std::isnan(L.z) ? 0.0f : rmax(0.0f, L.z);
+            L = v3(rmin(c.x, clampv), rmin(c.y, clampv), rmin(c.z, clampv));
+        }
+        acc = add(acc, L);  // Tile::add_sample, film.h:66-70
+        wsum += 1.0f;
+    }
+    return sampler;
 }
 
 int hw_threads(int n) {
@@ -790,6 +833,102 @@ void orc_cosine_hemisphere(const float *u2, int32_t n, float *out3) {
     }
 }
 
+// ---- unit entry points: one call of a static function above per input row (tests/golden/path_kat.json)
+static inline V3 ld3(const float *p) { return v3(p[0], p[1], p[2]); }
+static inline void st3(float *p, V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+
+void orc_unit_disk(const float *u2, int32_t n, float *out2) {
+    for (int i = 0; i < n; i++) {
+        V2 d = concentric_disk(V2{u2[2 * i], u2[2 * i + 1]});
+        out2[2 * i] = d.x; out2[2 * i + 1] = d.y;
+    }
+}
+
+void orc_unit_frame(const float *n3, const float *w3, int32_t n, float *out12) {
+    for (int i = 0; i < n; i++) {
+        Frame f = make_frame(ld3(n3 + 3 * i));
+        st3(out12 + 12 * i, f.t);
+        st3(out12 + 12 * i + 3, f.b);
+        st3(out12 + 12 * i + 6, to_local(f, ld3(w3 + 3 * i)));
+        st3(out12 + 12 * i + 9, to_world(f, ld3(w3 + 3 * i)));
+    }
+}
+
+void orc_unit_ggx(const float *alpha, const float *v3_, const float *m3, int32_t n, float *out2) {
+    for (int i = 0; i < n; i++) {
+        out2[2 * i] = ggx_d(alpha[i], ld3(m3 + 3 * i));
+        out2[2 * i + 1] = ggx_g1(alpha[i], ld3(v3_ + 3 * i), ld3(m3 + 3 * i));
+    }
+}
+
+void orc_unit_sample_wh(const float *alpha, const float *wo3, const float *u2, int32_t n, float *out3) {
+    for (int i = 0; i < n; i++) st3(out3 + 3 * i, ggx_sample_wh(alpha[i], ld3(wo3 + 3 * i), V2{u2[2 * i], u2[2 * i + 1]}));
+}
+
+void orc_unit_closure_eval(int32_t kind, const float *R3, const float *alpha, const float *wo3, const float *wi3,
+                           int32_t n, float *out3) {
+    for (int i = 0; i < n; i++) {
+        Closure c{kind, ld3(R3 + 3 * i), alpha[i]};
+        st3(out3 + 3 * i, closure_eval(c, ld3(wo3 + 3 * i), ld3(wi3 + 3 * i)));
+    }
+}
+
+void orc_unit_closure_sample(int32_t kind, const float *R3, const float *alpha, const float *u2, const float *wo3,
+                             int32_t n, float *out7) {
+    for (int i = 0; i < n; i++) {
+        Closure c{kind, ld3(R3 + 3 * i), alpha[i]};
+        V3 wi = v3(0, 0, 0);
+        float pdf = 0;
+        V3 f = closure_sample(c, V2{u2[2 * i], u2[2 * i + 1]}, ld3(wo3 + 3 * i), wi, pdf);
+        st3(out7 + 7 * i, f);
+        st3(out7 + 7 * i + 3, wi);
+        out7[7 * i + 6] = pdf;
+    }
+}
+
+void orc_unit_select_material(const orc_scene *s, int32_t mat, const float *u, const float *tc2, int32_t n,
+                              int32_t *out_mat, float *out2) {
+    for (int i = 0; i < n; i++) {
+        const akr_material *m = &s->materials[mat];
+        float su = u[i];
+        float pdf = select_material(*s, m, su, V2{tc2[2 * i], tc2[2 * i + 1]});
+        out_mat[i] = (int32_t)(m - s->materials);
+        out2[2 * i] = pdf; out2[2 * i + 1] = su;
+    }
+}
+
+void orc_unit_texture(const orc_scene *s, int32_t tex, const float *tc2, int32_t n, float *out3) {
+    for (int i = 0; i < n; i++) st3(out3 + 3 * i, tex_eval(*s, tex, V2{tc2[2 * i], tc2[2 * i + 1]}));
+}
+
+void orc_unit_triangle(const orc_scene *s, uint32_t gid, const float *uv2, int32_t n, float *out12) {
+    Tri t = get_triangle(*s, gid);
+    for (int i = 0; i < n; i++) {
+        float u = uv2[2 * i], v = uv2[2 * i + 1];
+        st3(out12 + 12 * i, lerp3(t.v[0], t.v[1], t.v[2], u, v));
+        st3(out12 + 12 * i + 3, tri_ng(t));
+        st3(out12 + 12 * i + 6, lerp3(t.n[0], t.n[1], t.n[2], u, v));
+        V2 tc = lerp3(t.tc[0], t.tc[1], t.tc[2], u, v);
+        out12[12 * i + 9] = tc.x; out12[12 * i + 10] = tc.y;
+        out12[12 * i + 11] = tri_area(t);
+    }
+}
+
+void orc_unit_light_sample(const orc_scene *s, uint32_t gid, const float *u2, const float *p3, int32_t n,
+                           float *out15) {
+    Tri t = get_triangle(*s, gid);
+    for (int i = 0; i < n; i++) {
+        LightSample ls = light_sample(*s, t, V2{u2[2 * i], u2[2 * i + 1]}, ld3(p3 + 3 * i));
+        float *o = out15 + 15 * i;
+        st3(o, ls.wi);
+        o[3] = ls.pdf;
+        st3(o + 4, ls.L);
+        st3(o + 7, ls.shadow.o);
+        st3(o + 10, ls.shadow.d);
+        o[13] = ls.shadow.tmin; o[14] = ls.shadow.tmax;
+    }
+}
+
 int orc_trace(const orc_scene *s, const akr_ray *rays, uint64_t n, orc_hit *hits, int any_hit, int32_t tight,
               int32_t n_threads, uint64_t *box_tests, uint64_t *tri_tests) {
     int T = hw_threads(n_threads);
@@ -837,29 +976,17 @@ int orc_render_probe(const orc_scene *s, const akr_pt_params *p, const akr_rect 
     const std::vector<Work> work = split_work(tiles, n_tiles, W, H);
     int T = hw_threads(n_threads);
     std::vector<PathStats> pst(T);
-    const float clampv = p->ray_clamp;
     const bool tight = !(p->flags & AKR_PT_EXACT_CULL);
     TileFilm tf(work);
     parallel_for(work.size(), T, 1, [&](uint64_t wi, int tid) {
         const Work &w = work[wi];
         for (int y = w.y0; y < w.y1; y++)
             for (int x = w.x0; x < w.x1; x++) {
-                Lcg sampler{(uint32_t)(x + y * W)};  // set_sample_index(x + y * W), integrator.cpp:124
-                V3 acc = v3(0, 0, 0);
-                float wsum = 0;
+                V3 acc;
+                float wsum;
                 PixelTally pt;
-                for (int sidx = 0; sidx < p->spp; sidx++) {
-                    V3 L = trace_path(sc, sampler, x, y, p->max_depth, tight, pst[tid], pt);
-                    if (clampv > 0) {  // gpu/cuda/integrator.cpp:397-398 (GPU-only clamp)
-                        V3 c;
-                        c.x = std::isnan(L.x) ? 0.0f : rmax(0.0f, L.x);
-                        c.y = std::isnan(L.y) ? 0.0f : rmax(0.0f, L.y);
-                        c.z = std::isnan(L.z) ? 0.0f : rmax(0.0f, L.z);
-                        L = v3(rmin(c.x, clampv), rmin(c.y, clampv), rmin(c.z, clampv));
-                    }
-                    acc = add(acc, L);  // Tile::add_sample, film.h:66-70
-                    wsum += 1.0f;
-                }
+                // set_sample_index(x + y * W), integrator.cpp:124
+                Lcg sampler = pixel_samples(sc, *p, x, y, (uint32_t)(x + y * W), tight, pst[tid], acc, wsum, pt);
                 float *o = tf.at(wi, w, x, y);
                 o[0] = acc.x;
                 o[1] = acc.y;
@@ -884,6 +1011,34 @@ int orc_render_probe(const orc_scene *s, const akr_pt_params *p, const akr_rect 
             stats->box_tests += q.box;
             stats->tri_tests += q.tri;
         }
+    }
+    return 0;
+}
+
+int orc_render_pixels(const orc_scene *s, const akr_pt_params *p, const int32_t *xy, int32_t n, float *radiance,
+                      float *weight, akr_pixel_probe *probe) {
+    Scene sc;
+    sc.s = s;
+    sc.cam = make_camera(s->camera);
+    if (s->n_lights > 0) {
+        sc.dist.build(s->light_power, (size_t)s->n_lights);
+        for (int i = 0; i < s->n_lights; i++) sc.lights.push_back(get_triangle(*s, s->light_gid[i]));
+    }
+    const bool tight = !(p->flags & AKR_PT_EXACT_CULL);
+    PathStats st;
+    for (int i = 0; i < n; i++) {
+        const int x = xy[2 * i], y = xy[2 * i + 1];
+        V3 acc;
+        float wsum;
+        PixelTally pt;
+        // the seed in unsigned arithmetic: x + y * W passes 2^31 in a 65535-wide frame
+        Lcg sampler = pixel_samples(sc, *p, x, y, (uint32_t)x + (uint32_t)y * (uint32_t)sc.cam.w, tight, st, acc, wsum, pt);
+        radiance[3 * i] = acc.x; radiance[3 * i + 1] = acc.y; radiance[3 * i + 2] = acc.z;
+        weight[i] = wsum;
+        probe[i].seed = sampler.seed;
+        probe[i].closest_rays = pt.closest;
+        probe[i].shadow_rays = pt.shadow;
+        probe[i].flags = AKR_PROBE_SEED | AKR_PROBE_RAYS;
     }
     return 0;
 }

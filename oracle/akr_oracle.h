@@ -9,8 +9,13 @@
  * (LCG, Distribution1D, Moller-Trumbore, camera), (b) the reference's own test
  * tests/test-math.cpp:49-58 (Frame round trip), (c) the reference's own fixtures
  * (resources/data/cornell_box/CornellBox-Original.obj.mesh and ref.png, loose statistical
- * check only: ref.png's render settings are unknown).  Pixel-level parity against the reference
- * binary is therefore "partially pinned" — see DESIGN.md §5.
+ * check only: ref.png's render settings are unknown), (d) an independent second reading of the
+ * reference's camera, warps, Frame, GGX, closures, material selection, textures, triangles, area
+ * light, light list and path loop in numpy f32 (tests/golden/ref_restate.py), whose function
+ * vectors (path_kat.json, through the orc_unit_* entries below) and per-pixel renders
+ * (path_golden_*.npz) this file must equal bit for bit (tests/test_path_kat_host.py).  Still
+ * unpinned: the reference binary itself, glibc's own sinf / cosf / atanf, and BVH construction
+ * order (the goldens use a brute-force intersection) — see DESIGN.md §5.
  */
 #ifndef AKR_ORACLE_H
 #define AKR_ORACLE_H
@@ -81,6 +86,33 @@ void orc_frame_roundtrip(const float *n3, const float *w3, float *local_to_world
 /* Cosine-hemisphere / concentric disk warps (kernel/sampling.h:32-53). */
 void orc_cosine_hemisphere(const float *u2, int32_t n, float *out3);
 
+/* Unit entry points for tests/golden/path_kat.json: each runs one of the restatement's own
+ * functions (the ones orc_render uses) on n input rows.
+ *  disk             concentric_disk_sampling (sampling.h:32-46): u2 -> out2
+ *  frame            Frame(n) (math.h:201-225): out12 = T, B, world_to_local(w), local_to_world(w)
+ *  ggx              GGX_D(alpha, m), GGX_G1(alpha, v, m) (microfacet.h:74-89): out2 = D, G1
+ *  sample_wh        MicrofacetModel::sample_wh, EGGX (microfacet.h:125-149)
+ *  closure_eval     kind 1 DiffuseBSDF / 2 MicrofacetReflection ::evaluate (material.h:69-74, 103-120)
+ *  closure_sample   ::sample (material.h:76-85, 122-137): out7 = f, wi, pdf
+ *  select_material  Material::select_material (material.h:255-271): resolved material, out2 = pdf, u
+ *  texture          Texture::evaluate (texture.h:30-66, image.hpp:83-99)
+ *  triangle         Triangle p, ng, ns, texcoord, area (shape.h:32-42): out12 = p, ng, ns, tc, area
+ *  light_sample     AreaLight::sample (light.h:58-71): out15 = wi, pdf, L, shadow o, d, tmin, tmax */
+void orc_unit_disk(const float *u2, int32_t n, float *out2);
+void orc_unit_frame(const float *n3, const float *w3, int32_t n, float *out12);
+void orc_unit_ggx(const float *alpha, const float *v3, const float *m3, int32_t n, float *out2);
+void orc_unit_sample_wh(const float *alpha, const float *wo3, const float *u2, int32_t n, float *out3);
+void orc_unit_closure_eval(int32_t kind, const float *R3, const float *alpha, const float *wo3,
+                           const float *wi3, int32_t n, float *out3);
+void orc_unit_closure_sample(int32_t kind, const float *R3, const float *alpha, const float *u2,
+                             const float *wo3, int32_t n, float *out7);
+void orc_unit_select_material(const orc_scene *s, int32_t mat, const float *u, const float *tc2,
+                              int32_t n, int32_t *out_mat, float *out2);
+void orc_unit_texture(const orc_scene *s, int32_t tex, const float *tc2, int32_t n, float *out3);
+void orc_unit_triangle(const orc_scene *s, uint32_t gid, const float *uv2, int32_t n, float *out12);
+void orc_unit_light_sample(const orc_scene *s, uint32_t gid, const float *u2, const float *p3,
+                           int32_t n, float *out15);
+
 /* Closest-hit (any_hit = 0) or occlusion (any_hit = 1) over the scene BVH with the reference
  * traversal (bvh-accelerator.h:488-547); tight = 0 is the reference's intersectAABB bit for bit,
  * tight = 1 also rejects boxes behind the origin (the device default); n_threads <= 0 -> all. */
@@ -102,6 +134,11 @@ int orc_render(const orc_scene *s, const akr_pt_params *p, const akr_rect *tiles
 int orc_render_probe(const orc_scene *s, const akr_pt_params *p, const akr_rect *tiles, int32_t n_tiles,
                      float *radiance, float *weight, int32_t n_threads, orc_render_stats *stats,
                      akr_pixel_probe *probe);
+/* The same per-pixel loop for n listed pixels (x, y pairs) into packed outputs radiance[3 * n],
+ * weight[n], probe[n]: nothing is sized by the frame, so single pixels of a 65535 x 65535 camera
+ * (whose seeds x + y * W reach almost every sampler state) can be checked. */
+int orc_render_pixels(const orc_scene *s, const akr_pt_params *p, const int32_t *xy, int32_t n,
+                      float *radiance, float *weight, akr_pixel_probe *probe);
 /* cpu::AmbientOcclusion::render (kernel/integrators/cpu/integrator.cpp:40-87) over the pixels of
  * `tiles`, same work split; L is 1 when the cosine-sampled ray from the camera hit (frame of the
  * geometric normal, tmin Eps) has no closest hit with t < occlude, 0 otherwise or on a camera miss.

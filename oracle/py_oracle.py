@@ -13,7 +13,9 @@ from pathlib import Path
 import numpy as np
 
 HERE = Path(__file__).resolve().parent
-LIB = HERE / "_build" / "libakr_oracle.so"
+# AKR_ORACLE_LIB points the binding at another build of the oracle (a mutated scratch copy, to show
+# that the known-answer tests bite); unset, it is the library oracle/Makefile builds
+LIB = Path(os.environ.get("AKR_ORACLE_LIB") or HERE / "_build" / "libakr_oracle.so")
 
 _P = C.c_void_p
 
@@ -68,9 +70,72 @@ def lib():
         l.orc_render.argtypes = [C.POINTER(OrcScene), _P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(OrcStats)]
         l.orc_render_probe.argtypes = [C.POINTER(OrcScene), _P, _P, C.c_int32, _P, _P, C.c_int32,
                                        C.POINTER(OrcStats), _P]
+        l.orc_render_pixels.argtypes = [C.POINTER(OrcScene), _P, _P, C.c_int32, _P, _P, _P]
         l.orc_render_ao.argtypes = [C.POINTER(OrcScene), _P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(OrcStats)]
+        for name, args in (("orc_unit_disk", [_P, C.c_int32, _P]),
+                           ("orc_unit_frame", [_P, _P, C.c_int32, _P]),
+                           ("orc_unit_ggx", [_P, _P, _P, C.c_int32, _P]),
+                           ("orc_unit_sample_wh", [_P, _P, _P, C.c_int32, _P]),
+                           ("orc_unit_closure_eval", [C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
+                           ("orc_unit_closure_sample", [C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
+                           ("orc_unit_select_material", [C.POINTER(OrcScene), C.c_int32, _P, _P, C.c_int32, _P, _P]),
+                           ("orc_unit_texture", [C.POINTER(OrcScene), C.c_int32, _P, C.c_int32, _P]),
+                           ("orc_unit_triangle", [C.POINTER(OrcScene), C.c_uint32, _P, C.c_int32, _P]),
+                           ("orc_unit_light_sample", [C.POINTER(OrcScene), C.c_uint32, _P, _P, C.c_int32, _P])):
+            getattr(l, name).argtypes = args
+            getattr(l, name).restype = None
         _lib = l
     return _lib
+
+
+def _rows(a, k):
+    return np.ascontiguousarray(a, np.float32).reshape(-1, k)
+
+
+def unit_disk(u2):
+    u2 = _rows(u2, 2)
+    out = np.zeros((len(u2), 2), np.float32)
+    lib().orc_unit_disk(_p(u2), len(u2), _p(out))
+    return out
+
+
+def unit_frame(n3, w3):
+    """-> [n, 12]: T, B, world_to_local(w), local_to_world(w) of Frame(n)."""
+    n3, w3 = _rows(n3, 3), _rows(w3, 3)
+    out = np.zeros((len(n3), 12), np.float32)
+    lib().orc_unit_frame(_p(n3), _p(w3), len(n3), _p(out))
+    return out
+
+
+def unit_ggx(alpha, v3, m3):
+    """-> [n, 2]: GGX_D(alpha, m), GGX_G1(alpha, v, m)."""
+    alpha, v3, m3 = np.ascontiguousarray(alpha, np.float32).reshape(-1), _rows(v3, 3), _rows(m3, 3)
+    out = np.zeros((len(alpha), 2), np.float32)
+    lib().orc_unit_ggx(_p(alpha), _p(v3), _p(m3), len(alpha), _p(out))
+    return out
+
+
+def unit_sample_wh(alpha, wo3, u2):
+    alpha, wo3, u2 = np.ascontiguousarray(alpha, np.float32).reshape(-1), _rows(wo3, 3), _rows(u2, 2)
+    out = np.zeros((len(alpha), 3), np.float32)
+    lib().orc_unit_sample_wh(_p(alpha), _p(wo3), _p(u2), len(alpha), _p(out))
+    return out
+
+
+def unit_closure_eval(kind, R3, alpha, wo3, wi3):
+    """kind 1 diffuse, 2 microfacet -> f [n, 3]."""
+    R3, alpha, wo3, wi3 = _rows(R3, 3), np.ascontiguousarray(alpha, np.float32).reshape(-1), _rows(wo3, 3), _rows(wi3, 3)
+    out = np.zeros((len(alpha), 3), np.float32)
+    lib().orc_unit_closure_eval(int(kind), _p(R3), _p(alpha), _p(wo3), _p(wi3), len(alpha), _p(out))
+    return out
+
+
+def unit_closure_sample(kind, R3, alpha, u2, wo3):
+    """-> [n, 7]: f, wi, pdf."""
+    R3, alpha, u2, wo3 = _rows(R3, 3), np.ascontiguousarray(alpha, np.float32).reshape(-1), _rows(u2, 2), _rows(wo3, 3)
+    out = np.zeros((len(alpha), 7), np.float32)
+    lib().orc_unit_closure_sample(int(kind), _p(R3), _p(alpha), _p(u2), _p(wo3), len(alpha), _p(out))
+    return out
 
 
 def _p(a):
@@ -198,6 +263,33 @@ class OracleScene:
         lib().orc_trace_brute(C.byref(self.s), _p(rays), rays.shape[0], _p(hits), int(any_hit), n_threads)
         return hits
 
+    def unit_select_material(self, mat, u, tc2):
+        """-> (resolved global material index [n], [n, 2]: choice pdf, rescaled u)."""
+        u, tc2 = np.ascontiguousarray(u, np.float32).reshape(-1), _rows(tc2, 2)
+        om, out = np.zeros(len(u), np.int32), np.zeros((len(u), 2), np.float32)
+        lib().orc_unit_select_material(C.byref(self.s), int(mat), _p(u), _p(tc2), len(u), _p(om), _p(out))
+        return om, out
+
+    def unit_texture(self, tex, tc2):
+        tc2 = _rows(tc2, 2)
+        out = np.zeros((len(tc2), 3), np.float32)
+        lib().orc_unit_texture(C.byref(self.s), int(tex), _p(tc2), len(tc2), _p(out))
+        return out
+
+    def unit_triangle(self, gid, uv2):
+        """-> [n, 12]: p, ng, ns, texcoord, area."""
+        uv2 = _rows(uv2, 2)
+        out = np.zeros((len(uv2), 12), np.float32)
+        lib().orc_unit_triangle(C.byref(self.s), int(gid), _p(uv2), len(uv2), _p(out))
+        return out
+
+    def unit_light_sample(self, gid, u2, p3):
+        """-> [n, 15]: wi, pdf, L, shadow ray o, d, tmin, tmax."""
+        u2, p3 = _rows(u2, 2), _rows(p3, 3)
+        out = np.zeros((len(u2), 15), np.float32)
+        lib().orc_unit_light_sample(C.byref(self.s), int(gid), _p(u2), _p(p3), len(u2), _p(out))
+        return out
+
     def render(self, spp, max_depth, tiles=None, ray_clamp=0.0, n_threads=0, radiance=None, weight=None,
                exact_cull=False, probe=False):
         """cpu::PathTracer::render restated; with probe=True also returns the frame-indexed per-pixel
@@ -220,6 +312,16 @@ class OracleScene:
         if probe:
             return radiance, weight, stats, pr
         return radiance, weight, stats
+
+    def render_pixels(self, xy, spp, max_depth, ray_clamp=0.0):
+        """orc_render_pixels: the listed pixels into packed (radiance [n, 3], weight [n], probe [n])."""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n = len(xy)
+        rad, w = np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        pr = np.zeros(n, self.capi.PROBE_DTYPE)
+        p = self.capi.PtParams(int(spp), int(max_depth), float(ray_clamp), 0)
+        lib().orc_render_pixels(C.byref(self.s), C.byref(p), _p(xy), n, _p(rad), _p(w), _p(pr))
+        return rad, w, pr
 
     def render_ao(self, spp, tiles=None, occlude=float("inf"), n_threads=0, radiance=None, weight=None,
                   exact_cull=False):

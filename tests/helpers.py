@@ -118,6 +118,103 @@ def textured_scene(resolution=(48, 48)):
     return sc
 
 
+def branches_scene(resolution=(24, 24)):
+    """Twelve triangles that reach the path loop's rare branches (tests/golden/make_path_golden.py
+    counts them): a glossy floor of roughness 0.05 seen at grazing angles, half of it with its
+    shading normals turned down; a Mix(0.5, Diffuse, Emissive) back wall; a nested Mix side wall; a
+    one-sided ceiling light; a triangle without a material; a one-sided emitter seen from its back;
+    a double-sided emitter; and, last in the light list, a zero-area emissive triangle.  No right
+    wall: rays leave the scene there."""
+    ct = scene.ConstantTexture
+    diffuse = scene.DiffuseMaterial(ct([0.6, 0.5, 0.4]))
+    glossy = scene.GlossyMaterial(ct([0.9, 0.85, 0.8]), ct([0.05, 0.05, 0.05]))
+    mats = [glossy,
+            scene.MixMaterial(ct([0.5, 0.5, 0.5]), diffuse, scene.EmissiveMaterial(ct([5.0, 5.0, 5.0]))),
+            scene.MixMaterial(ct([0.3, 0.3, 0.3]),
+                              scene.MixMaterial(ct([0.5, 0.5, 0.5]), diffuse,
+                                                scene.GlossyMaterial(ct([0.7, 0.7, 0.9]), ct([0.5, 0.5, 0.5]))),
+                              scene.DiffuseMaterial(ct([0.2, 0.6, 0.3]))),
+            scene.EmissiveMaterial(ct([20.0, 18.0, 15.0])),
+            scene.EmissiveMaterial(ct([4.0, 1.0, 1.0])),
+            scene.EmissiveMaterial(ct([1.0, 4.0, 1.0]), double_sided=True),
+            scene.EmissiveMaterial(ct([3.0, 3.0, 3.0]))]
+    quad_tc = [[0, 0, 1, 0, 1, 1], [0, 0, 1, 1, 0, 1]]
+    tri_tc = [0, 0, 1, 0, 0, 1]
+    tris = [  # (three vertices, shading normal, texcoords, material slot)
+        ([(-2, 0, 4), (2, 0, 4), (2, 0, -2)], (0, 1, 0), quad_tc[0], 0),            # floor
+        ([(-2, 0, 4), (2, 0, -2), (-2, 0, -2)], (0, -1, 0), quad_tc[1], 0),         # floor, normals down
+        ([(-2, 0, -2), (2, 0, -2), (2, 3, -2)], (0, 0, 1), quad_tc[0], 1),          # back wall
+        ([(-2, 0, -2), (2, 3, -2), (-2, 3, -2)], (0, 0, 1), quad_tc[1], 1),
+        ([(-2, 0, 4), (-2, 0, -2), (-2, 3, -2)], (1, 0, 0), quad_tc[0], 2),         # left wall
+        ([(-2, 0, 4), (-2, 3, -2), (-2, 3, 4)], (1, 0, 0), quad_tc[1], 2),
+        ([(-1, 3, -1), (1, 3, -1), (1, 3, 1)], (0, -1, 0), quad_tc[0], 3),          # ceiling light, faces down
+        ([(-1, 3, -1), (1, 3, 1), (-1, 3, 1)], (0, -1, 0), quad_tc[1], 3),
+        ([(0.5, 0.5, 0), (1.5, 0.5, 0), (1.0, 1.5, 0)], (0, 0, 1), tri_tc, -1),     # no material
+        ([(-1.5, 0.5, 0.5), (-1.0, 1.5, 0.5), (-0.5, 0.5, 0.5)], (0, 0, -1), tri_tc, 4),   # faces away
+        ([(-0.25, 1.75, -0.5), (0.25, 1.75, -0.5), (0, 2.25, -0.5)], (0, 0, 1), tri_tc, 5),  # double sided
+        ([(1.0, 2.0, -1), (1.25, 2.25, -1), (1.5, 2.5, -1)], (0, 0, 1), tri_tc, 6),          # zero area
+    ]
+    verts = np.array([p for t in tris for p in t[0]], np.float32)
+    mesh = scene.Mesh(verts, np.arange(len(verts), dtype=np.int32).reshape(-1, 3),
+                      np.array([list(t[1]) * 3 for t in tris], np.float32),
+                      np.array([t[2] for t in tris], np.float32),
+                      np.array([t[3] for t in tris], np.int32), mats)
+    cam = scene.PerspectiveCamera(position=(0.3, 0.4, 3.9), rotation=(0.0, 0.0, 0.0), fov=70.0,
+                                  resolution=tuple(resolution))
+    return scene.Scene(camera=cam, shapes=[mesh])
+
+
+def kat_scene():
+    """The inputs of the function-level vectors (tests/golden/path_kat.json): one mesh whose
+    material slots hold image textures of odd sizes, Mix materials of fraction 0, 1 and 0.5, a
+    nested Mix, and emissive triangles seen face-on, edge-on and with zero area.  Every leaf
+    material has its own colour, which is how a vector names the material a Mix resolved to."""
+    ct = scene.ConstantTexture
+    rng = np.random.default_rng(5)
+    img = lambda h, w: scene.ImageTexture(rng.random((h, w, 4), dtype=np.float32))
+    d = lambda c: scene.DiffuseMaterial(ct([c, c, c]))
+    g = lambda c: scene.GlossyMaterial(ct([c, c, c]), ct([0.3, 0.3, 0.3]))
+    mats = [scene.DiffuseMaterial(img(5, 7)),                                   # 0
+            scene.DiffuseMaterial(img(3, 3)),                                   # 1
+            scene.DiffuseMaterial(img(1, 11)),                                  # 2
+            scene.MixMaterial(ct([0.0, 0.0, 0.0]), d(0.11), g(0.12)),           # 3
+            scene.MixMaterial(ct([1.0, 1.0, 1.0]), d(0.13), g(0.14)),           # 4
+            scene.MixMaterial(ct([0.5, 0.5, 0.5]), d(0.15), g(0.16)),           # 5
+            scene.MixMaterial(ct([0.25, 0.9, 0.9]),                             # 6: nested on both sides
+                              scene.MixMaterial(ct([0.5, 0.5, 0.5]), d(0.17), g(0.18)),
+                              scene.MixMaterial(img(4, 6), d(0.19), scene.EmissiveMaterial(ct([0.2, 0.2, 0.2])))),
+            scene.EmissiveMaterial(img(2, 3)),                                  # 7
+            scene.EmissiveMaterial(ct([3.0, 2.0, 1.0]), double_sided=True)]     # 8
+    tris = [
+        ([(0, 0, 0), (1, 0, 0), (0, 1, 0)], [(0, 0, 1)] * 3, [0, 0, 1, 0, 0, 1], 0),
+        ([(0.3, -1.2, 2.0), (1.7, 0.4, 2.5), (-0.9, 0.8, 3.1)], [(0.1, 0.2, 0.9), (-0.3, 0.1, 0.8), (0, 0, 1)],
+         [-0.5, 0.25, 1.75, 1.0, 0.5, -1.25], 1),
+        ([(-1, 2, -1), (1, 2, -1), (1, 2, 1)], [(0, -1, 0)] * 3, [0, 0, 1, 0, 1, 1], 7),      # light, faces down
+        ([(-1, 2, -1), (1, 2, 1), (-1, 2, 1)], [(0, -1, 0)] * 3, [0, 0, 1, 1, 0, 1], 8),
+        ([(2, 0, 0), (2.5, 0.5, 0), (3, 1, 0)], [(0, 0, 1)] * 3, [0, 0, 1, 0, 0, 1], 8),      # zero area
+        ([(4, 0, 0), (5, 0, 0), (4, 1, 0)], [(0, 0, 1)] * 3, [0, 0, 1, 0, 0, 1], 2),
+        ([(4, 0, 1), (5, 0, 1), (4, 1, 1)], [(0, 0, 1)] * 3, [0, 0, 1, 0, 0, 1], 3),
+        ([(4, 0, 2), (5, 0, 2), (4, 1, 2)], [(0, 0, 1)] * 3, [0, 0, 1, 0, 0, 1], 4),
+        ([(4, 0, 3), (5, 0, 3), (4, 1, 3)], [(0, 0, 1)] * 3, [0, 0, 1, 0, 0, 1], 5),
+        ([(4, 0, 4), (5, 0, 4), (4, 1, 4)], [(0, 0, 1)] * 3, [0.2, 0.1, 0.9, 0.3, 0.4, 0.8], 6),
+    ]
+    verts = np.array([p for t in tris for p in t[0]], np.float32)
+    mesh = scene.Mesh(verts, np.arange(len(verts), dtype=np.int32).reshape(-1, 3),
+                      np.array([[c for nrm in t[1] for c in nrm] for t in tris], np.float32),
+                      np.array([t[2] for t in tris], np.float32),
+                      np.array([t[3] for t in tris], np.int32), mats)
+    cam = scene.PerspectiveCamera(position=(0.5, 0.5, 8.0), rotation=(0.0, 0.0, 0.0), fov=40.0, resolution=(16, 16))
+    return scene.Scene(camera=cam, shapes=[mesh])
+
+
+def dark_scene(resolution=(8, 8)):
+    """The Cornell box with its light turned into a wall: no area light, so select_light's and
+    compute_direct_lighting's no-light branches run."""
+    sc = cornell(resolution)
+    sc.shapes[0].materials[7] = scene.DiffuseMaterial(scene.ConstantTexture([0.5, 0.5, 0.5]))
+    return sc
+
+
 def hits_to_gid(hits, mesh_base):
     gid = np.full(hits.shape[0], 0xFFFFFFFF, np.uint32)
     ok = hits["geom_id"] >= 0
