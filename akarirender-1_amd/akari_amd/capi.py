@@ -116,6 +116,11 @@ class AdaptiveInfo(C.Structure):
                 ("samples", C.c_uint64), ("strips", C.c_uint64), ("strips_at_cap", C.c_uint64)]
 
 
+class Environment(C.Structure):
+    _fields_ = [("resolution", C.c_int32), ("_pad", C.c_int32), ("scale", C.c_float * 3), ("select_prob", C.c_float),
+                ("world_to_env", C.c_float * 9)]
+
+
 class FeatureParams(C.Structure):
     _fields_ = [("spp", C.c_int32), ("flags", C.c_int32)]
 
@@ -173,6 +178,9 @@ EXPORTS = {
     "akr_hip_upload_textures": (C.c_int, [_P, _P, C.c_int32]),
     "akr_hip_upload_materials": (C.c_int, [_P, _P, C.c_int32]),
     "akr_hip_upload_lights": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "akr_hip_upload_environment": (C.c_int, [_P, C.POINTER(Environment), _P]),
+    "akr_hip_environment_sample": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P]),
+    "akr_hip_environment_eval": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "akr_hip_build_accel": (C.c_int, [_P, C.POINTER(BuildParams)]),
     "akr_hip_import_accel": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int32]),
     "akr_bvh_validate": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32)]),
@@ -415,6 +423,37 @@ class HipContext:
         arr = (AreaLight * max(1, len(lights)))(*[AreaLight(g, p) for g, p in lights])
         pw = np.ascontiguousarray(power, np.float32)
         self._check(self.lib.akr_hip_upload_lights(self.h, _arr_ptr(arr), len(lights), _ptr(pw)))
+
+    def upload_environment(self, rgb, scale=(1.0, 1.0, 1.0), select_prob=0.5, world_to_env=None):
+        """Environment light: rgb float32 [N, N, 3], an octahedral map of the sphere (row j, column i);
+        None removes it.  world_to_env: the 3x3 R of d_env = R d_world (identity by default)."""
+        if rgb is None:
+            self._check(self.lib.akr_hip_upload_environment(self.h, None, None))
+            return
+        m = np.ascontiguousarray(rgb, np.float32)
+        if m.ndim != 3 or m.shape[0] != m.shape[1] or m.shape[2] != 3:
+            raise ValueError(f"an environment map is [N, N, 3], not {m.shape}")
+        r = np.eye(3) if world_to_env is None else np.asarray(world_to_env, np.float64).reshape(3, 3)
+        e = Environment(m.shape[0], 0, (C.c_float * 3)(*[float(v) for v in np.broadcast_to(scale, 3)]),
+                        float(select_prob), (C.c_float * 9)(*[float(v) for v in r.reshape(-1)]))
+        self._check(self.lib.akr_hip_upload_environment(self.h, C.byref(e), _ptr(m)))
+
+    def environment_sample(self, u):
+        """u float32 [n, 2] -> (world directions [n, 3], sampled texels with the scale [n, 3], pdfs [n])
+        from the device functions the shading calls."""
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = u.shape[0]
+        d, rgb, pdf = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        self._check(self.lib.akr_hip_environment_sample(self.h, _ptr(u), n, _ptr(d), _ptr(rgb), _ptr(pdf)))
+        return d, rgb, pdf
+
+    def environment_eval(self, dirs):
+        """World directions float32 [n, 3] -> (the texel each looks up [n, 3], the pdf sampling gives it [n])."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = d.shape[0]
+        rgb, pdf = np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        self._check(self.lib.akr_hip_environment_eval(self.h, _ptr(d), n, _ptr(rgb), _ptr(pdf)))
+        return rgb, pdf
 
     def build_accel(self, max_leaf_size=4, n_bins=32, traversal_cost=1.0, intersect_cost=4.0, n_threads=0,
                     builder=0, spatial_budget=0.0, wide_collapse=0):

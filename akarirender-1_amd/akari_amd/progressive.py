@@ -173,6 +173,12 @@ def scene_fingerprint(cs) -> str:
     add("cam_rotation", cam.rotation, np.float32)
     add("cam_fov", [cam.fov], np.float64)
     add("cam_resolution", cam.resolution, np.int32)
+    env = getattr(cs, "environment", None)
+    if env is not None:  # a scene without one keeps the fingerprint it always had
+        add("env_map", env.map, np.float32)
+        add("env_scale", env.scale, np.float32)
+        add("env_select_prob", [env.select_prob], np.float32)
+        add("env_world_to_env", env.world_to_env, np.float32)
     return h.hexdigest()
 
 

@@ -39,7 +39,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import capi, denoise, film, progressive, scene
+from . import capi, denoise, envmap, film, progressive, scene
 from .dist import tile_grid
 
 
@@ -258,7 +258,19 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--denoise-variance", action="store_true",
                     help="with --denoise and one of --pass-spp, --preview, --adaptive: track each pixel's variance "
                          "from the passes and filter with the variance-guided filter")
+    ap.add_argument("--env", default=None, metavar="FILE",
+                    help="light the scene with this lat-long environment image (.pfm, .hdr, .npy); replaces the "
+                         "scene's EnvironmentLight")
+    ap.add_argument("--env-scale", type=float, default=None, metavar="S", help="multiply the environment by S")
+    ap.add_argument("--env-rotate", type=float, default=None, metavar="DEGREES",
+                    help="turn the environment about the vertical axis")
+    ap.add_argument("--env-res", type=int, default=None, metavar="N",
+                    help="resolution of the octahedral map made from a lat-long image, 1..2048")
     args = ap.parse_args(argv)
+    if args.env_res is not None and not 1 <= args.env_res <= 2048:  # refused before the scene is read
+        ap.error("--env-res needs 1..2048")
+    if args.env_scale is not None and not args.env_scale >= 0:
+        ap.error("--env-scale needs a number >= 0")
     if args.denoise_iters is not None:  # refused before the scene is read
         if not args.denoise:
             ap.error("--denoise-iters needs --denoise")
@@ -307,6 +319,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sc = scene.load_scene_file(args.scene)
     if args.spp is not None:
         sc.integrator.spp = args.spp
+    if args.env is not None:
+        try:
+            sc.environment = scene.EnvironmentLight(envmap.read_map(args.env), layout="latlong")
+        except (OSError, ValueError) as e:
+            ap.error(f"--env: {e}")
+    if sc.environment is None and (args.env_scale is not None or args.env_rotate is not None or args.env_res is not None):
+        ap.error("--env-scale, --env-rotate and --env-res need an environment (--env, or the scene's EnvironmentLight)")
+    if sc.environment is not None:
+        if args.env_scale is not None:
+            sc.environment.scale = (args.env_scale,) * 3
+        if args.env_rotate is not None:
+            sc.environment.rotation = (0.0, args.env_rotate, 0.0)
+        if args.env_res is not None:
+            sc.environment.resolution = args.env_res
     if passes and not isinstance(sc.integrator, scene.PathIntegrator):
         ap.error(f"--pass-spp, --preview, --time-budget, --checkpoint, --resume and --adaptive need the Path integrator; "
                  f"the scene's is {type(sc.integrator).__name__}")

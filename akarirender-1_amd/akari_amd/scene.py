@@ -101,12 +101,23 @@ class AOIntegrator:             # core/nodes/integrator.cpp:26-49
     occlude: float = math.inf
 
 
+@dataclass(eq=False)
+class EnvironmentLight:         # DESIGN.md section 3.17 (the reference has no environment light)
+    image: np.ndarray           # float32 [N, N, 3] ("octahedral") or [h, w, 3] ("latlong", +y up)
+    layout: str = "octahedral"
+    scale: Sequence[float] = (1.0, 1.0, 1.0)
+    rotation: Sequence[float] = (0.0, 0.0, 0.0)   # Euler degrees or a 3x3 (envmap.rotation_matrix)
+    select_prob: float = 0.5    # its share of the direct-lighting draws beside area lights
+    resolution: int = 0         # of the octahedral map made from a lat-long image (0: min(h, 2048))
+
+
 @dataclass
 class Scene:                    # SceneNode (core/nodes/scene.h)
     camera: PerspectiveCamera
     shapes: List[Mesh]
     integrator: object = field(default_factory=PathIntegrator)
     output: str = "out.png"
+    environment: Optional[EnvironmentLight] = None
 
 
 # ----------------------------------------------------------------------------- .mesh I/O
@@ -187,6 +198,47 @@ def texture_integral(tex: Texture) -> np.float32:
 
 
 @dataclass
+class CompiledEnvironment:
+    """An EnvironmentLight as akr_hip_upload_environment takes it."""
+    map: np.ndarray                 # float32 [N, N, 3], octahedral
+    scale: np.ndarray               # float32 [3]
+    select_prob: float
+    world_to_env: np.ndarray        # float32 [3, 3], computed in double
+
+
+def compile_environment(env: EnvironmentLight, n_lights: int = 0) -> CompiledEnvironment:
+    """Validate an EnvironmentLight and bring it to the octahedral layout (the library refuses the same
+    maps; here the message names the scene's field)."""
+    from . import envmap
+    img = np.asarray(env.image, np.float32)
+    if img.ndim != 3 or img.shape[2] < 3:
+        raise ValueError(f"EnvironmentLight: the image is [h, w, 3], not {img.shape}")
+    img = img[..., :3]
+    if env.layout == "latlong":
+        n = int(env.resolution) if env.resolution else min(int(img.shape[0]), 2048)
+        if not 1 <= n <= 2048:
+            raise ValueError(f"EnvironmentLight: resolution {n} is outside [1, 2048]")
+        img = envmap.latlong_to_octahedral(img, n)
+    elif env.layout != "octahedral":
+        raise ValueError(f"EnvironmentLight: unknown layout {env.layout!r} (octahedral, latlong)")
+    n = img.shape[0]
+    if img.shape[1] != n or not 1 <= n <= 2048:
+        raise ValueError(f"EnvironmentLight: an octahedral map is N x N with 1 <= N <= 2048, not {img.shape[:2]}")
+    if not np.all(np.isfinite(img)) or np.any(img < 0):
+        raise ValueError("EnvironmentLight: the map has a negative or non-finite texel")
+    scale = np.broadcast_to(np.asarray(env.scale, np.float32), (3,)).copy()
+    if not np.all(np.isfinite(scale)) or np.any(scale < 0):
+        raise ValueError("EnvironmentLight: scale must be finite and not negative")
+    if not np.any(img * scale > 0):
+        raise ValueError("EnvironmentLight: the map is black everywhere: nothing to sample")
+    if not 0.0 < float(env.select_prob) < 1.0:
+        raise ValueError(f"EnvironmentLight: select_prob {env.select_prob} must be inside (0, 1)"
+                         + (" (the scene has area lights)" if n_lights else ""))
+    r = envmap.rotation_matrix(env.rotation).astype(np.float32)
+    return CompiledEnvironment(np.ascontiguousarray(img, np.float32), scale, float(env.select_prob), r)
+
+
+@dataclass
 class CompiledScene:
     """Flat render scene (Scene<C>, kernel/scene.h:50-91): meshes concatenated."""
     vertices: np.ndarray            # float32 [nv, 3]
@@ -204,6 +256,7 @@ class CompiledScene:
     power: np.ndarray               # float32
     camera: PerspectiveCamera
     meshes: List[Mesh]
+    environment: Optional["CompiledEnvironment"] = None
 
     @property
     def n_tris(self) -> int:
@@ -289,7 +342,8 @@ def compile_scene(scene: Scene) -> CompiledScene:
         matid=cat(mids, (0,), np.int32), mesh_base=np.array(mesh_base, np.uint32), mesh_slots=slots_all,
         materials=materials, textures=textures, images=images, lights=lights,
         light_gid=np.array(light_gid, np.uint32), power=np.array(power, np.float32),
-        camera=scene.camera, meshes=list(scene.shapes))
+        camera=scene.camera, meshes=list(scene.shapes),
+        environment=compile_environment(scene.environment, len(lights)) if scene.environment is not None else None)
 
 
 def _light_power(mesh: Mesh, prim: int, m: EmissiveMaterial) -> np.float32:
@@ -314,6 +368,7 @@ def upload_scene(ctx: "capi.HipContext", cs: CompiledScene, build: bool = True, 
                             cs.mesh_slots[geom_id])
         assert g == geom_id
     ctx.upload_lights(cs.lights, cs.power)
+    upload_environment(ctx, cs.environment)
     cam = cs.camera
     ctx.set_camera(cam.position, cam.rotation, cam.fov, cam.resolution)
     if bvh is not None:
@@ -321,6 +376,14 @@ def upload_scene(ctx: "capi.HipContext", cs: CompiledScene, build: bool = True, 
     if build:
         return ctx.build_accel(**build_kw)
     return None
+
+
+def upload_environment(ctx: "capi.HipContext", env: Optional[CompiledEnvironment]):
+    """The scene's environment, or its removal from a context that held another scene's."""
+    if env is not None:
+        ctx.upload_environment(env.map, env.scale, env.select_prob, env.world_to_env)
+    elif hasattr(ctx.lib, "akr_hip_upload_environment"):   # an experiment library may predate the entry point
+        ctx.upload_environment(None)
 
 
 # ----------------------------------------------------------------------------- .akari loader
@@ -585,9 +648,29 @@ class SdlParser:
             return it
         if t == "AO":
             return AOIntegrator(int(f.get("spp", 16)), float(f.get("occlude", math.inf)))
+        if t == "EnvironmentLight":
+            from . import envmap
+            if not isinstance(f.get("image"), str):
+                self._err("EnvironmentLight needs image: a file name (.pfm, .hdr, .npy)")
+            try:
+                img = envmap.read_map(self.path.parent / f["image"])
+            except (OSError, ValueError) as e:
+                self._err(str(e))
+            sc = f.get("scale", 1.0)
+            env = EnvironmentLight(img, layout=f.get("layout", "latlong"),
+                                   scale=tuple(float(F32(x)) for x in (sc if isinstance(sc, list) else [sc] * 3)),
+                                   rotation=tuple(float(x) for x in f.get("rotation", [0.0, 0.0, 0.0])),
+                                   select_prob=float(f.get("select_prob", 0.5)), resolution=int(f.get("resolution", 0)))
+            if env.layout not in ("latlong", "octahedral") or len(env.scale) != 3 or len(env.rotation) != 3:
+                self._err("EnvironmentLight: layout is latlong or octahedral, scale a number or 3, rotation 3 angles")
+            return env
         if t == "Scene":
+            env = f.get("environment")
+            if env is not None and not isinstance(env, EnvironmentLight):
+                self._err("Scene.environment must be an EnvironmentLight")
             return Scene(camera=f["camera"], shapes=list(f.get("shapes", [])),
-                         integrator=f.get("integrator", PathIntegrator()), output=f.get("output", "out.png"))
+                         integrator=f.get("integrator", PathIntegrator()), output=f.get("output", "out.png"),
+                         environment=env)
         return _Obj(t, f)
 
 

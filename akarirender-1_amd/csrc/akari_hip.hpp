@@ -238,6 +238,24 @@ class HipPathTracer {
               "render");
     }
 
+    // Environment light (include/akr_hip.h): an n x n octahedral map (rgb: 3 n n floats,
+    // row-major), lit by importance-sampled direct lighting and seen by camera rays that leave the scene.
+    // world_to_env: row-major 3x3 of d_env = R d_world, or null for the identity.  Renders of a scene with an
+    // environment take the wavefront form.  Ends the render session, like every upload.
+    static void set_environment(const HipAccelerator &scene, int n, const float *rgb, const float *world_to_env = nullptr,
+                                float scale = 1.0f, float select_prob = 0.5f) {
+        akr_environment e{};
+        e.resolution = n;
+        e.select_prob = select_prob;
+        for (int c = 0; c < 3; c++) e.scale[c] = scale;
+        for (int c = 0; c < 9; c++) e.world_to_env[c] = world_to_env ? world_to_env[c] : (c % 4 == 0 ? 1.0f : 0.0f);
+        if (!rgb) throw std::runtime_error("set_environment: null map (clear_environment removes one)");
+        check(scene.handle(), akr_hip_upload_environment(scene.handle(), &e, rgb), "upload_environment");
+    }
+    static void clear_environment(const HipAccelerator &scene) {
+        check(scene.handle(), akr_hip_upload_environment(scene.handle(), nullptr, nullptr), "upload_environment");
+    }
+
     // Render sessions (include/akr_hip.h): the accelerator's context remembers its last render(), and
     // render_continue adds `more` samples per pixel from where it stopped; the film is cleared and then
     // holds the session's totals, bit for bit the film of one render() of all the samples.

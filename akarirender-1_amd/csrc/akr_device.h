@@ -195,6 +195,37 @@ struct ShadeArgs {
     int32_t last;                  // no extension ray is traced after this bounce
 };
 
+// Environment light: an N x N octahedral map of the sphere over [-1, 1]^2 and the
+// tables of its piecewise-constant distribution, built on the host (capi.hip) with the sequential f32
+// sums of Distribution1D.  The pdf tables hold func[k] / (func_int * N), the discrete pdf of
+// Distribution1D::sample_discrete, so a sample reads one value instead of two and divides nothing.
+struct EnvDev {
+    const AKR_GLOBAL float4 *map;       // texel (i, j) at j * n + i: rgb as uploaded (scale is applied at the lookup)
+    const AKR_GLOBAL float *marg_cdf;   // n + 1: the rows' marginal
+    const AKR_GLOBAL float *marg_pdf;   // n
+    const AKR_GLOBAL float *cond_cdf;   // n rows of n + 1: the columns' conditional of each row
+    const AKR_GLOBAL float *cond_pdf;   // n rows of n
+    int32_t n;
+    float select_prob;                  // with area lights: the environment is taken when su.x < select_prob
+    float scale[3];
+    float R[9];                         // row-major: d_env = R d_world
+};
+
+// k_shade_env: k_shade's arguments and the environment, which today's k_shade does not carry
+struct ShadeEnvArgs {
+    ShadeArgs s;
+    EnvDev env;
+};
+
+// The unit entry points (akr_hip_environment_sample / _eval): n inputs (2 floats u, or 3 floats of a
+// world direction) -> world direction (sample only), texel rgb with the scale applied, solid-angle pdf
+struct EnvUnitArgs {
+    EnvDev env;
+    const float *in;
+    uint32_t n;
+    float *dir, *rgb, *pdf;
+};
+
 // One AO bounce (cpu/integrator.cpp:46-56) for every queued camera hit: appends the AO ray to
 // ray_out (+ colour (1,1,1, slot) for a shadow-mode trace, or the slot for a closest-hit trace).
 struct AoShadeArgs {

@@ -212,6 +212,17 @@ struct akr_hip_ctx {
     CameraDev cam{};
     bool cam_set = false;
 
+    // Environment light: the map and the tables of its distribution, built by
+    // akr_hip_upload_environment; env.n == 0: none.  A scene with one renders in the wavefront form.
+    EnvDev env{};
+    DBuf<float4> d_env_map;
+    DBuf<float> d_env_tab;  // marginal CDF, marginal pdf, conditional CDFs, conditional pdfs
+    bool env_on() const { return env.n > 0; }
+    const EnvDev &require_env() const {
+        if (!env_on()) throw std::runtime_error("no environment light (akr_hip_upload_environment)");
+        return env;
+    }
+
     // path / queue buffers
     size_t cap = 0;
     // The last render's tile list, clipped, non-empty tiles only: (x0, y0, width, first slot).  The
@@ -1134,7 +1145,9 @@ struct akr_hip_ctx {
         // kernel measured faster there (textured hall 11.5 vs 16.0 ms per 4K spp)
         const bool use_path = opt.path_kernel == 1 || (opt.path_kernel == 2 && (int64_t)M <= opt.path_auto_pixels &&
                                                        (simple_shading || opt.path_auto_complex));
-        if (use_path && tight && opt.wide && trace_args(nullptr).lean) {
+        // an environment light is shaded by the wavefront's k_shade_env alone, whatever
+        // `path` says: the precedent exact_cull and a non-lean view set
+        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_on()) {
             if (p.spp > 0) render_path(pass);
             last_passes = 1;
         } else {
@@ -1324,7 +1337,8 @@ struct akr_hip_ctx {
                 sh.max_depth = p.max_depth;
                 sh.last = b == nb - 1;
                 sh.probe = probe_p;
-                timed("shade", ms, [&] { launch_shade(sh, (uint32_t)M, ms); });
+                if (env_on()) timed("shade", ms, [&] { launch_shade_env(ShadeEnvArgs{sh, env}, (uint32_t)M, ms); });
+                else timed("shade", ms, [&] { launch_shade(sh, (uint32_t)M, ms); });
                 HIPCHK(hipEventRecord(ev_shade[sq], ms));
                 HIPCHK(hipStreamWaitEvent(side, ev_shade[sq], 0));
                 if (b < p.max_depth) {
@@ -1742,6 +1756,133 @@ int akr_hip_upload_lights(akr_hip_ctx *ctx, const akr_area_light *lights, int32_
         ctx->scene_dirty = true;
         ctx->drop_session();
     });
+}
+
+namespace {
+// Distribution1D (common/distribution.h:46-64) over func[0..n): the sequential f32 sums, the CDF
+// divided by the integral (or uniform when that is 0), and sample_discrete's pdf func / (integral * n)
+// (0 for a function that is 0 everywhere, which no draw selects).  Returns the integral.
+float env_dist1d(const float *func, int n, float *cdf, float *pdf) {
+    const float fn = (float)n;
+    cdf[0] = 0.0f;
+    for (int i = 0; i < n; i++) cdf[i + 1] = cdf[i] + func[i] / fn;
+    const float fi = cdf[n];
+    for (int i = 1; i <= n; i++) cdf[i] = fi == 0.0f ? (float)i / fn : cdf[i] / fi;
+    for (int i = 0; i < n; i++) pdf[i] = fi == 0.0f ? 0.0f : func[i] / (fi * fn);
+    return fi;
+}
+// |q|_2 of the octahedron's point over (x, y) of the square: env_decode's len (kernels.hip), same operations
+float env_len(float x, float y) {
+    const float z = (1.0f - std::fabs(x)) - std::fabs(y);
+    if (z < 0.0f) {
+        const float fx = (1.0f - std::fabs(y)) * (x < 0.0f ? -1.0f : 1.0f);
+        const float fy = (1.0f - std::fabs(x)) * (y < 0.0f ? -1.0f : 1.0f);
+        x = fx;
+        y = fy;
+    }
+    float s = x * x;
+    s += y * y;
+    s += z * z;
+    return std::sqrt(s);
+}
+
+void env_unit(akr_hip_ctx *ctx, bool sample, const float *in, uint64_t n, float *dir, float *rgb, float *pdf) {
+    const EnvDev &env = ctx->require_env();
+    if (n == 0) return;
+    if (!in || !rgb || !pdf || (sample && !dir)) throw std::runtime_error("environment: null buffer");
+    if (n > (1ull << 28)) throw std::runtime_error("environment: too many inputs in one call");
+    const size_t k = sample ? 2 : 3;
+    DBuf<float> d_in, d_out;  // out: dir (3n), rgb (3n), pdf (n)
+    hipStream_t st = ctx->stream;
+    ctx->serialize(st);
+    d_in.upload(in, k * n, st);
+    d_out.reserve(7 * n);
+    EnvUnitArgs a{};
+    a.env = env;
+    a.in = d_in.p;
+    a.n = (uint32_t)n;
+    a.dir = d_out.p;
+    a.rgb = d_out.p + 3 * n;
+    a.pdf = d_out.p + 6 * n;
+    launch_env_unit(sample, a, st);
+    HIPCHK(hipGetLastError());
+    if (sample) HIPCHK(hipMemcpyAsync(dir, a.dir, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rgb, a.rgb, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pdf, a.pdf, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+}
+}  // namespace
+
+int akr_hip_upload_environment(akr_hip_ctx *ctx, const akr_environment *e, const float *rgb) {
+    return guard(ctx, [&] {
+        // no render of this context may still read the tables that are replaced here
+        if (ctx->done_recorded) HIPCHK(hipEventSynchronize(ctx->ev_done));
+        ctx->drop_session();
+        if (!rgb) {  // remove
+            ctx->env = EnvDev{};
+            return;
+        }
+        if (!e) throw std::runtime_error("environment: null description");
+        const int n = e->resolution;
+        if (n < 1 || n > 2048) throw std::runtime_error("environment: resolution must be in [1, 2048]");
+        if (!(e->select_prob > 0.0f && e->select_prob < 1.0f))
+            throw std::runtime_error("environment: select_prob must be inside (0, 1)");
+        for (int c = 0; c < 3; c++)
+            if (!std::isfinite(e->scale[c]) || e->scale[c] < 0.0f)
+                throw std::runtime_error("environment: scale must be finite and not negative");
+        for (int c = 0; c < 9; c++)
+            if (!std::isfinite(e->world_to_env[c])) throw std::runtime_error("environment: world_to_env is not finite");
+        const size_t nn = (size_t)n * n;
+        for (size_t k = 0; k < 3 * nn; k++)
+            if (!std::isfinite(rgb[k]) || rgb[k] < 0.0f)
+                throw std::runtime_error("environment: texel " + std::to_string(k / 3) + " is negative or not finite");
+        // f_ij = luminance(texel * scale) / |q_c|^3 at the texel's centre; one conditional per row, the
+        // marginal over the rows' integrals (host: a device scan would round differently)
+        const float fn = (float)n;
+        const size_t o_mcdf = 0, o_mpdf = o_mcdf + n + 1, o_ccdf = o_mpdf + n, o_cpdf = o_ccdf + (size_t)n * (n + 1);
+        std::vector<float> tab(o_cpdf + nn), func(n), rows(n);
+        std::vector<float4> map(nn);
+        for (int j = 0; j < n; j++) {
+            const float yc = (((float)j + 0.5f) / fn) * 2.0f - 1.0f;
+            for (int i = 0; i < n; i++) {
+                const float xc = (((float)i + 0.5f) / fn) * 2.0f - 1.0f;
+                const float *t = rgb + 3 * ((size_t)j * n + i);
+                map[(size_t)j * n + i] = make_float4(t[0], t[1], t[2], 0.0f);
+                float lum = (t[0] * e->scale[0]) * 0.2126f;  // Color::luminance, common/color.h:52-55
+                lum += (t[1] * e->scale[1]) * 0.7152f;
+                lum += (t[2] * e->scale[2]) * 0.0722f;
+                const float len = env_len(xc, yc);
+                func[i] = lum / ((len * len) * len);
+            }
+            rows[j] = env_dist1d(func.data(), n, &tab[o_ccdf + (size_t)j * (n + 1)], &tab[o_cpdf + (size_t)j * n]);
+        }
+        const float total = env_dist1d(rows.data(), n, &tab[o_mcdf], &tab[o_mpdf]);
+        if (!(total > 0.0f) || !std::isfinite(total))
+            throw std::runtime_error("environment: the map's luminance is zero everywhere (or overflows): nothing to sample");
+        ctx->d_env_map.upload(map.data(), map.size(), ctx->stream);
+        ctx->d_env_tab.upload(tab.data(), tab.size(), ctx->stream);
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // the staging vectors end here
+        EnvDev d{};
+        d.map = (decltype(d.map))ctx->d_env_map.p;
+        const float *tp = ctx->d_env_tab.p;
+        d.marg_cdf = (decltype(d.marg_cdf))(tp + o_mcdf);
+        d.marg_pdf = (decltype(d.marg_pdf))(tp + o_mpdf);
+        d.cond_cdf = (decltype(d.cond_cdf))(tp + o_ccdf);
+        d.cond_pdf = (decltype(d.cond_pdf))(tp + o_cpdf);
+        d.n = n;
+        d.select_prob = e->select_prob;
+        for (int c = 0; c < 3; c++) d.scale[c] = e->scale[c];
+        for (int c = 0; c < 9; c++) d.R[c] = e->world_to_env[c];
+        ctx->env = d;
+    });
+}
+
+int akr_hip_environment_sample(akr_hip_ctx *ctx, const float *u, uint64_t n, float *dir, float *rgb, float *pdf) {
+    return guard(ctx, [&] { env_unit(ctx, true, u, n, dir, rgb, pdf); });
+}
+
+int akr_hip_environment_eval(akr_hip_ctx *ctx, const float *dir, uint64_t n, float *rgb, float *pdf) {
+    return guard(ctx, [&] { env_unit(ctx, false, dir, n, nullptr, rgb, pdf); });
 }
 
 namespace {

@@ -6,6 +6,8 @@
 //   k_raygen           camera rays for every path slot (pathtracer.h:61-64, camera.h:67-86)
 //   k_shade            hit -> emission / BSDF sample / NEE light sample, wave-ballot compaction
 //                      of live paths and shadow rays (pathtracer.h:69-132, 137-162)
+//   k_shade_env        the same with an environment light: the depth-0 miss sees the
+//                      map, direct lighting samples it
 //   k_splat            Tile::add_sample per pixel, in sample order (core/film.h:66-70)
 //
 // Numerics: f32 with the reference's operation order (akr_math.h); the library is built with
@@ -1007,10 +1009,100 @@ __device__ __forceinline__ int select_light_index(const SceneDev &s, const Tab &
     return li < 0 ? 0 : (li > s.n_lights - 1 ? s.n_lights - 1 : li);
 }
 
-template <class Tab>
+// ------------------------------------------------------------------------ environment light
+// DESIGN.md §3.17.  Add, multiply, divide, sqrt, abs and compare only: each step is the same IEEE
+// operation in the numpy restatement (tests/golden/env_restate.py).
+__device__ __forceinline__ float env_sgn(float x) { return x < 0.0f ? -1.0f : 1.0f; }  // sgn 0 = +1
+// the lower hemisphere's fold of the square's corners
+__device__ __forceinline__ void env_fold(float &x, float &y) {
+    const float fx = (1.0f - fabsf(y)) * env_sgn(x);
+    const float fy = (1.0f - fabsf(x)) * env_sgn(y);
+    x = fx;
+    y = fy;
+}
+// point of the square -> unit direction (map space); len = |q|_2 of the point q of the octahedron
+__device__ __forceinline__ V3 env_decode(float x, float y, float &len) {
+    const float z = (1.0f - fabsf(x)) - fabsf(y);
+    if (z < 0.0f) env_fold(x, y);
+    const V3 q = v3(x, y, z);
+    len = sqrtf(dot(q, q));
+    return divs(q, len);
+}
+__device__ __forceinline__ int env_texel(float x, int n) {
+    const int i = (int)((x * 0.5f + 0.5f) * (float)n);
+    return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+}
+// direction (map space) -> texel (i, j); len as in env_decode
+__device__ __forceinline__ void env_encode(int n, V3 d, int &i, int &j, float &len) {
+    const float l1 = (fabsf(d.x) + fabsf(d.y)) + fabsf(d.z);
+    const V3 q = divs(d, l1);
+    len = sqrtf(dot(q, q));
+    float x = q.x, y = q.y;
+    if (q.z < 0.0f) env_fold(x, y);
+    i = env_texel(x, n);
+    j = env_texel(y, n);
+}
+__device__ __forceinline__ V3 env_to_map(const EnvDev &e, V3 d) {  // R d
+    return v3(dot(v3(e.R[0], e.R[1], e.R[2]), d), dot(v3(e.R[3], e.R[4], e.R[5]), d), dot(v3(e.R[6], e.R[7], e.R[8]), d));
+}
+__device__ __forceinline__ V3 env_to_world(const EnvDev &e, V3 d) {  // R^T d
+    return v3(dot(v3(e.R[0], e.R[3], e.R[6]), d), dot(v3(e.R[1], e.R[4], e.R[7]), d), dot(v3(e.R[2], e.R[5], e.R[8]), d));
+}
+__device__ __forceinline__ V3 env_lookup(const EnvDev &e, int i, int j) {
+    const float4 t = e.map[(size_t)j * (size_t)e.n + (size_t)i];
+    return v3(t.x * e.scale[0], t.y * e.scale[1], t.z * e.scale[2]);
+}
+// p_omega of a point of texel (i, j) whose q has length len: P_ij (N^2 / 4) len^3
+__device__ __forceinline__ float env_pdf(const EnvDev &e, int i, int j, float len) {
+    const float P = e.marg_pdf[j] * e.cond_pdf[(size_t)j * (size_t)e.n + (size_t)i];
+    // a texel no draw selects (u = 1 clamps into a black last column, whose in-texel offset is 0 / 0):
+    // the pdf is 0 whatever the point, and the sample is skipped
+    if (!(P > 0.0f)) return 0.0f;
+    const float fn = (float)e.n;
+    return (P * ((fn * fn) * 0.25f)) * ((len * len) * len);
+}
+// Distribution1D::sample_discrete's index (distribution.h:32-44): upper_bound over the CDF, clamped
+template <class P>  // a float pointer in any address space
+__device__ __forceinline__ int env_search(P cdf, int n, float u) {
+    int lo = 0, hi = n + 1;
+    while (lo < hi) {
+        const int m = (lo + hi) / 2;
+        if (cdf[m] <= u) lo = m + 1; else hi = m;
+    }
+    const int k = hi - 1;
+    return k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
+}
+struct EnvSample {
+    V3 wi;      // world direction
+    V3 Le;      // the sampled texel's radiance, never a re-encode of wi
+    float pdf;  // solid angle
+};
+template <class MP>  // mcdf: the marginal CDF, e.marg_cdf or a workgroup's LDS copy of it (same values)
+__device__ __forceinline__ EnvSample env_sample(const EnvDev &e, V2 u, MP mcdf) {
+    const int n = e.n;
+    const int j = env_search(mcdf, n, u.y);
+    const float r0 = mcdf[j], r1 = mcdf[j + 1];
+    const float oy = (u.y - r0) / (r1 - r0);
+    const AKR_GLOBAL float *row = e.cond_cdf + (size_t)j * (size_t)(n + 1);
+    const int i = env_search(row, n, u.x);
+    const float c0 = row[i], c1 = row[i + 1];
+    const float ox = (u.x - c0) / (c1 - c0);
+    const float fn = (float)n;
+    const float x = (((float)i + ox) / fn) * 2.0f - 1.0f;
+    const float y = (((float)j + oy) / fn) * 2.0f - 1.0f;
+    float len;
+    const V3 d = env_decode(x, y, len);
+    EnvSample s;
+    s.pdf = env_pdf(e, i, j, len);
+    s.Le = env_lookup(e, i, j);
+    s.wi = env_to_world(e, d);
+    return s;
+}
+
+template <class Tab, bool ENV = false>
 __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab, uint32_t gid, float u, float v, V3 wo,
                                               V3 beta, uint32_t &seed, int depth, int max_depth, bool last, Bounce &o,
-                                              unsigned long long *t_load = nullptr) {
+                                              unsigned long long *t_load = nullptr, const EnvDev *env = nullptr) {
     o.emit = o.ext = o.sh = false;
     unsigned long long t0 = 0;  // counting builds (t_load): ticks until the shading record is in
     if (t_load) t0 = wall_clock64();
@@ -1085,9 +1177,37 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
     const V3 ev_beta = divs(muls(f, cng), pdf);
     // select_light(sampler.next2d()) — scene.h:79-90
     const V2 su = lcg_next2(seed);
-    if (s.n_lights > 0) {
-        const auto &lt = *tab.light(select_light_index(s, tab, su.x));
-        const V2 lu = lcg_next2(seed);
+    bool area = s.n_lights > 0;
+    float sel_x = su.x;  // the area lights' selection draw
+    float keep = 1.0f;   // and what the environment's share leaves of their selection pdf
+    V2 lu{0.0f, 0.0f};
+    if constexpr (ENV) {
+        // one light of {environment, area lights}: lu is drawn either way
+        lu = lcg_next2(seed);
+        const float sp = env->select_prob;
+        if (!area || su.x < sp) {
+            const EnvSample es = env_sample(*env, lu, env->marg_cdf);
+            const float sel_pdf = area ? sp : 1.0f;
+            area = false;
+            if (!(es.pdf <= 0.0f)) {
+                const V3 fe = closure_eval(cl, to_local(frame, wo), to_local(frame, es.wi));
+                const V3 fl = muls(mul(es.Le, fe), fabsf(dot(ns, es.wi)));
+                const V3 col = divs(mul(beta, fl), sel_pdf * es.pdf);
+                if (!is_black(col)) {  // from p towards the sky: unoccluded when nothing is hit at all
+                    o.sh = true;
+                    o.s0 = make_float4(p.x, p.y, p.z, kEps / fabsf(dot(ng, es.wi)));
+                    o.s1 = make_float4(es.wi.x, es.wi.y, es.wi.z, kInf);
+                    o.col = col;
+                }
+            }
+        } else {  // the remap select_material uses
+            sel_x = (su.x - sp) / (1.0f - sp);
+            keep = 1.0f - sp;
+        }
+    }
+    if (area) {
+        const auto &lt = *tab.light(select_light_index(s, tab, sel_x));
+        if constexpr (!ENV) lu = lcg_next2(seed);
         // AreaLight::sample (light.h:58-71); lng, the area and the selection pdf are precomputed
         const float su0 = sqrtf(lu.x);
         const float b0 = 1 - su0, b1 = lu.y * su0;
@@ -1105,7 +1225,9 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
         }
         const float lpdf = dist_sqr / rmax(0.0f, -dot(lwi, lng)) / lt.area_half;
         if (!(lpdf <= 0.0f)) {
-            const float light_pdf = lt.sel_pdf * lpdf;
+            float light_sel = lt.sel_pdf;
+            if constexpr (ENV) light_sel = light_sel * keep;
+            const float light_pdf = light_sel * lpdf;
             const V3 fe = closure_eval(cl, to_local(frame, wo), to_local(frame, lwi));
             const V3 fl = muls(mul(Le, fe), fabsf(dot(ns, lwi)));
             const V3 col = divs(mul(beta, fl), light_pdf);
@@ -1136,7 +1258,8 @@ __device__ __forceinline__ void shade_hit(const SceneDev &s, uint32_t gid, float
 #define AKR_SHADE_BLOCK 256
 #endif
 constexpr int kShadeBlock = AKR_SHADE_BLOCK;  // threads per shade workgroup (one queue atomic each)
-__global__ __launch_bounds__(kShadeBlock) void k_shade(ShadeArgs a) {
+template <bool ENV>
+__device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *env) {
     const uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x;
     const uint32_t n = *a.count_in;
     if (blockIdx.x * kShadeBlock >= n) return;  // whole workgroup past the queue (uniform: before any barrier)
@@ -1151,13 +1274,31 @@ __global__ __launch_bounds__(kShadeBlock) void k_shade(ShadeArgs a) {
         const uint32_t gid = fbits(hv.w);
         if (gid != kNoHit) {  // miss -> on_miss (no-op), the path ends
             const float4 rdv = a.ray_in[2 * (size_t)i + 1];
-            shade_hit(a.sc, gid, hv.y, hv.z, neg(v3(rdv.x, rdv.y, rdv.z)), V3{stv.x, stv.y, stv.z}, seed, a.depth,
-                      a.max_depth, a.last != 0, bo);
+            if constexpr (ENV)
+                shade_hit_tab<GlobalTab, true>(a.sc, global_tab(a.sc), gid, hv.y, hv.z, neg(v3(rdv.x, rdv.y, rdv.z)),
+                                               V3{stv.x, stv.y, stv.z}, seed, a.depth, a.max_depth, a.last != 0, bo,
+                                               nullptr, env);
+            else
+                shade_hit(a.sc, gid, hv.y, hv.z, neg(v3(rdv.x, rdv.y, rdv.z)), V3{stv.x, stv.y, stv.z}, seed, a.depth,
+                          a.max_depth, a.last != 0, bo);
             if (bo.emit) {
                 float4 l = a.L[slot];
                 l.x += bo.e.x;
                 l.y += bo.e.y;
                 l.z += bo.e.z;
+                a.L[slot] = l;
+            }
+        } else if constexpr (ENV) {
+            if (a.depth == 0) {  // a camera ray that leaves the scene sees the map; deeper misses add nothing
+                const float4 rdv = a.ray_in[2 * (size_t)i + 1];
+                int ti, tj;
+                float len;
+                env_encode(env->n, env_to_map(*env, v3(rdv.x, rdv.y, rdv.z)), ti, tj, len);
+                const V3 e = mul(V3{stv.x, stv.y, stv.z}, env_lookup(*env, ti, tj));
+                float4 l = a.L[slot];
+                l.x += e.x;
+                l.y += e.y;
+                l.z += e.z;
                 a.L[slot] = l;
             }
         }
@@ -1184,6 +1325,36 @@ __global__ __launch_bounds__(kShadeBlock) void k_shade(ShadeArgs a) {
         a.shadow_ray[2 * (size_t)spos + 1] = bo.s1;
         a.shadow_color[spos] = make_float4(bo.col.x, bo.col.y, bo.col.z, bitsf(slot));
     }
+}
+__global__ __launch_bounds__(kShadeBlock) void k_shade(ShadeArgs a) { shade_queue<false>(a, nullptr); }
+// with an environment light: the depth-0 miss and the environment's branch of direct lighting
+__global__ __launch_bounds__(kShadeBlock) void k_shade_env(ShadeEnvArgs a) { shade_queue<true>(a.s, &a.env); }
+
+// the unit entry points: the device functions the shading calls, one input per thread
+__global__ __launch_bounds__(kBlock) void k_env_sample(EnvUnitArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const EnvSample s = env_sample(a.env, V2{a.in[2 * (size_t)i], a.in[2 * (size_t)i + 1]}, a.env.marg_cdf);
+    a.dir[3 * (size_t)i] = s.wi.x;
+    a.dir[3 * (size_t)i + 1] = s.wi.y;
+    a.dir[3 * (size_t)i + 2] = s.wi.z;
+    a.rgb[3 * (size_t)i] = s.Le.x;
+    a.rgb[3 * (size_t)i + 1] = s.Le.y;
+    a.rgb[3 * (size_t)i + 2] = s.Le.z;
+    a.pdf[i] = s.pdf;
+}
+__global__ __launch_bounds__(kBlock) void k_env_eval(EnvUnitArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const V3 d = v3(a.in[3 * (size_t)i], a.in[3 * (size_t)i + 1], a.in[3 * (size_t)i + 2]);
+    int ti, tj;
+    float len;
+    env_encode(a.env.n, env_to_map(a.env, d), ti, tj, len);
+    const V3 Le = env_lookup(a.env, ti, tj);
+    a.rgb[3 * (size_t)i] = Le.x;
+    a.rgb[3 * (size_t)i + 1] = Le.y;
+    a.rgb[3 * (size_t)i + 2] = Le.z;
+    a.pdf[i] = env_pdf(a.env, ti, tj, len);
 }
 
 // --------------------------------------------------------------------------- ambient occlusion
@@ -3226,6 +3397,16 @@ void launch_shade(const ShadeArgs &a, uint32_t max_items, hipStream_t st) {
     if (max_items == 0) return;
     const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
     hipLaunchKernelGGL(k_shade, grid, dim3(kShadeBlock), 0, st, a);
+}
+void launch_shade_env(const ShadeEnvArgs &a, uint32_t max_items, hipStream_t st) {
+    if (max_items == 0) return;
+    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
+    hipLaunchKernelGGL(k_shade_env, grid, dim3(kShadeBlock), 0, st, a);
+}
+void launch_env_unit(bool sample, const EnvUnitArgs &a, hipStream_t st) {
+    if (a.n == 0) return;
+    if (sample) hipLaunchKernelGGL(k_env_sample, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL(k_env_eval, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
 }
 void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, uint32_t *gate, hipStream_t st) {
     hipLaunchKernelGGL(k_pick_form, dim3(1), dim3(64), 0, st, sum, thresh, gate);

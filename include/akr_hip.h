@@ -242,6 +242,30 @@ int akr_hip_upload_textures(akr_hip_ctx *ctx, const akr_texture *textures, int32
 int akr_hip_upload_materials(akr_hip_ctx *ctx, const akr_material *materials, int32_t n);
 int akr_hip_upload_lights(akr_hip_ctx *ctx, const akr_area_light *lights, int32_t n,
                           const float *power);
+
+/* Environment light: an N x N octahedral map of the sphere over the square
+ * [-1, 1]^2, RGB f32, row-major, nearest-texel lookup, importance-sampled in direct lighting and seen by
+ * camera rays that leave the scene.  rgb: resolution * resolution * 3 floats, finite and >= 0, not black
+ * everywhere; null removes the environment.  scale multiplies every texel; world_to_env is the row-major
+ * 3x3 R of d_env = R d_world; select_prob, inside (0, 1), is the share of the direct-lighting draws the
+ * environment takes in a scene that also has area lights.  The distribution's tables are built on the host
+ * here.  Ends the render session, as every upload does.  A context with an environment renders in the
+ * wavefront form whatever option "path" says (akr_hip_render_form reports it). */
+typedef struct akr_environment {
+    int32_t resolution;
+    int32_t _pad;
+    float scale[3];
+    float select_prob;
+    float world_to_env[9];
+} akr_environment;
+int akr_hip_upload_environment(akr_hip_ctx *ctx, const akr_environment *env, const float *rgb);
+/* What the map does, through the device functions the shading calls; host buffers, synchronous.
+ * sample: u[2n] in [0, 1]^2 -> world directions dir[3n], the sampled texels with the scale applied rgb[3n]
+ * and the solid-angle pdfs pdf[n].  eval: world directions dir[3n] -> the texel each one looks up and the
+ * pdf with which sampling draws it. */
+int akr_hip_environment_sample(akr_hip_ctx *ctx, const float *u, uint64_t n, float *dir, float *rgb, float *pdf);
+int akr_hip_environment_eval(akr_hip_ctx *ctx, const float *dir, uint64_t n, float *rgb, float *pdf);
+
 int akr_hip_build_accel(akr_hip_ctx *ctx, const akr_build_params *params);
 /* Adopt a BVH2 built elsewhere (the arrays akr_hip_accel_export writes: akr_bvh_node[n_nodes],
  * akr_bvh_tri[n_tris]) for the uploaded meshes, instead of building one: the same wide view and
