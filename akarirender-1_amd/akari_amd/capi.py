@@ -319,10 +319,14 @@ def validate_bvh(nodes, tris, n_scene_tris):
 
 
 def render_node(ctxs, spp, max_depth, tiles, width, height, ray_clamp=0.0, exact_cull=False, radiance=None,
-                weight=None):
+                weight=None, mis=None):
     """akr_hip_render_node: tile j on ctxs[j % len(ctxs)], one host thread per context; returns
-    the full-frame (radiance, weight) accumulated like HipContext.render (into the given buffers)."""
+    the full-frame (radiance, weight) accumulated like HipContext.render (into the given buffers).
+    mis (True / False): option "mis" is set to it on every context first."""
     lib = load_library()
+    if mis is not None:
+        for c in ctxs:
+            c.set_option("mis", 1 if mis else 0)
     if radiance is None:
         radiance = np.zeros((height, width, 3), np.float32)
     if weight is None:

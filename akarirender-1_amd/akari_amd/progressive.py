@@ -145,8 +145,9 @@ def render_adaptive(ctx: "capi.HipContext", cap_spp: int, max_depth: int, tiles,
     return rad, wt, info
 
 
-def scene_fingerprint(cs) -> str:
-    """SHA-256 over a CompiledScene's arrays and camera: what a film's samples depend on."""
+def scene_fingerprint(cs, mis: bool = False) -> str:
+    """SHA-256 over a CompiledScene's arrays and camera, and the `mis` switch when it is on: what a film's
+    samples depend on."""
     h = hashlib.sha256()
 
     def add(tag, a, dtype):
@@ -173,6 +174,8 @@ def scene_fingerprint(cs) -> str:
     add("cam_rotation", cam.rotation, np.float32)
     add("cam_fov", [cam.fov], np.float64)
     add("cam_resolution", cam.resolution, np.int32)
+    if mis:  # a render without it keeps the fingerprint it always had
+        add("mis", [1], np.int32)
     env = getattr(cs, "environment", None)
     if env is not None:  # a scene without one keeps the fingerprint it always had
         add("env_map", env.map, np.float32)
@@ -204,12 +207,12 @@ class Checkpoint:
     FORMAT_VERSION = 1
 
     @classmethod
-    def capture(cls, ctx: "capi.HipContext", cs, tiles) -> "Checkpoint":
-        """The context's session, rendered over `tiles` of the compiled scene `cs`."""
+    def capture(cls, ctx: "capi.HipContext", cs, tiles, mis: bool = False) -> "Checkpoint":
+        """The context's session, rendered over `tiles` of the compiled scene `cs` (`mis`: with option "mis")."""
         info = ctx.render_state_info()
         sampler, film = ctx.render_state_export()
         return cls(info["width"], info["height"], capi.rect_array(tiles), info["spp_done"], info["max_depth"],
-                   float(info["ray_clamp"]), info["flags"], sampler, film, scene_fingerprint(cs))
+                   float(info["ray_clamp"]), info["flags"], sampler, film, scene_fingerprint(cs, mis))
 
     def save(self, path) -> None:
         """Written under a temporary name and renamed: a reader never sees half a file."""
@@ -248,19 +251,24 @@ class Checkpoint:
             raise CheckpointError(f"{path}: {ck.sampler.size} sampler states but film of shape {ck.film.shape}")
         return ck
 
-    def check(self, cs, tiles, width: int, height: int) -> None:
+    def check(self, cs, tiles, width: int, height: int, mis: bool = False) -> None:
         """Raises CheckpointError unless the checkpoint was rendered from this scene, at this
-        resolution, over this tile list."""
+        resolution, over this tile list, with this value of the `mis` switch."""
         if (self.width, self.height) != (int(width), int(height)):
             raise CheckpointError(f"checkpoint resolution {self.width}x{self.height}, scene {width}x{height}")
         if not np.array_equal(capi.rect_array(tiles), self.tiles):
             raise CheckpointError("checkpoint tile list differs from the render's")
-        if scene_fingerprint(cs) != self.fingerprint:
+        if scene_fingerprint(cs, mis) != self.fingerprint:
+            if scene_fingerprint(cs, not mis) == self.fingerprint:
+                raise CheckpointError(f"checkpoint was rendered with mis {'off' if mis else 'on'}, the render asks for "
+                                      f"mis {'on' if mis else 'off'}: the two estimators do not continue one another")
             raise CheckpointError("checkpoint was rendered from another scene or camera (fingerprint differs)")
 
-    def restore(self, ctx: "capi.HipContext", cs, tiles) -> None:
-        """Establish the checkpoint's session on `ctx`, which holds the uploaded scene `cs`."""
+    def restore(self, ctx: "capi.HipContext", cs, tiles, mis: bool = False) -> None:
+        """Establish the checkpoint's session on `ctx`, which holds the uploaded scene `cs`; option "mis" is
+        set to `mis` first, since the session reads it when it starts."""
         w, h = (int(v) for v in cs.camera.resolution)
-        self.check(cs, tiles, w, h)
+        self.check(cs, tiles, w, h, mis)
+        ctx.set_option("mis", 1 if mis else 0)
         ctx.render_state_import(self.spp_done, self.max_depth, self.tiles, self.sampler, self.film,
                                 ray_clamp=self.ray_clamp, exact_cull=bool(self.flags & capi.PT_EXACT_CULL))

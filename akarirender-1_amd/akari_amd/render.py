@@ -111,6 +111,8 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[
     try:
         for c in ctxs:
             scene.upload_scene(c, cs, **build_kw)
+            if getattr(it, "mis", False):   # a session switch, read when the render starts
+                c.set_option("mis", 1)
         if isinstance(it, scene.AOIntegrator):
             if len(ctxs) != 1:
                 raise ValueError("the AO integrator renders on one device")
@@ -149,7 +151,7 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
     w, h = (int(v) for v in sc.camera.resolution)
     tiles = _tiles(sc, it.tile_size)
     if ck is not None:  # checked before a device is touched
-        ck.check(cs, tiles, w, h)
+        ck.check(cs, tiles, w, h, it.mis)
         if ck.max_depth != it.max_depth or ck.ray_clamp != float(np.float32(it.ray_clamp)) or ck.flags != 0:
             raise progressive.CheckpointError(
                 f"checkpoint was rendered with max_depth {ck.max_depth}, ray_clamp {ck.ray_clamp}, flags {ck.flags}; "
@@ -158,15 +160,16 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
             raise progressive.CheckpointError(f"checkpoint holds {ck.spp_done} spp, more than the {it.spp} asked for")
     with capi.HipContext(device) as ctx:
         scene.upload_scene(ctx, cs, **build_kw)
+        ctx.set_option("mis", 1 if it.mis else 0)   # before the restore: a session reads it when it starts
         if post is not None:
             post.start(ctx)   # before the restore: an imported film is the tracker's first batch
             post.bind(tiles, w, h)
         if ck is not None:
-            ck.restore(ctx, cs, tiles)
+            ck.restore(ctx, cs, tiles, it.mis)
 
         def each_pass(done, rad, wt):
             if checkpoint is not None:
-                progressive.Checkpoint.capture(ctx, cs, tiles).save(checkpoint)
+                progressive.Checkpoint.capture(ctx, cs, tiles, it.mis).save(checkpoint)
             if post is not None and post.per_pass:   # the feature pass and the filter keep the session
                 post.finish(ctx, rad, wt)
             return on_pass(done, rad, wt) if on_pass is not None else None
@@ -193,6 +196,7 @@ def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, mi
     w, h = (int(v) for v in sc.camera.resolution)
     with capi.HipContext(device) as ctx:
         scene.upload_scene(ctx, cs, **build_kw)
+        ctx.set_option("mis", 1 if it.mis else 0)
         tiles = _tiles(sc, it.tile_size)
         each = on_pass
         if post is not None:
@@ -264,6 +268,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--env-scale", type=float, default=None, metavar="S", help="multiply the environment by S")
     ap.add_argument("--env-rotate", type=float, default=None, metavar="DEGREES",
                     help="turn the environment about the vertical axis")
+    ap.add_argument("--mis", action="store_true",
+                    help="Path integrator: combine the light sample and the BSDF sample of direct lighting by the "
+                         "power heuristic (multiple importance sampling); the scene's `mis` field does the same")
     ap.add_argument("--env-res", type=int, default=None, metavar="N",
                     help="resolution of the octahedral map made from a lat-long image, 1..2048")
     args = ap.parse_args(argv)
@@ -319,6 +326,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sc = scene.load_scene_file(args.scene)
     if args.spp is not None:
         sc.integrator.spp = args.spp
+    if args.mis:
+        if not isinstance(sc.integrator, scene.PathIntegrator):
+            ap.error(f"--mis needs the Path integrator; the scene's is {type(sc.integrator).__name__}")
+        sc.integrator.mis = True
     if args.env is not None:
         try:
             sc.environment = scene.EnvironmentLight(envmap.read_map(args.env), layout="latlong")

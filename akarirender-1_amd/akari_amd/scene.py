@@ -93,6 +93,9 @@ class PathIntegrator:           # core/nodes/integrator.cpp:50-84
     tile_size: int = 256
     ray_clamp: float = 10.0
     wavefront: bool = True
+    # multiple importance sampling of lights.  Not one of the reference node's fields, so a
+    # class attribute and no dataclass field: set `it.mis = True` on the instance
+    mis = False
 
 
 @dataclass
@@ -645,6 +648,10 @@ class SdlParser:
                 it.wavefront = bool(f["wavefront"])
             if "megakernel" in f:
                 it.wavefront = not bool(f["megakernel"])
+            if "mis" in f:
+                if not isinstance(f["mis"], bool) and f["mis"] not in (0, 1):
+                    self._err("Path: mis needs true or false")
+                it.mis = bool(f["mis"])
             return it
         if t == "AO":
             return AOIntegrator(int(f.get("spp", 16)), float(f.get("occlude", math.inf)))

@@ -373,6 +373,11 @@ class HipPathTracer {
     void track_variance(const HipAccelerator &scene, bool on = true) const {
         check(scene.handle(), akr_hip_set_option(scene.handle(), "film_variance", on ? 1 : 0), "track_variance");
     }
+    // Multiple importance sampling of lights (option "mis", include/akr_hip.h): before the
+    // render that starts the session; a continue keeps the session's value.
+    void set_mis(const HipAccelerator &scene, bool on = true) const {
+        check(scene.handle(), akr_hip_set_option(scene.handle(), "mis", on ? 1 : 0), "set_mis");
+    }
     void render_variance(const HipAccelerator &scene, const Film &film, std::vector<float> &variance) const {
         variance.assign(4 * (size_t)film.width * film.height, 0.0f);
         check(scene.handle(), akr_hip_render_variance(scene.handle(), variance.data()), "render_variance");

@@ -217,6 +217,26 @@ struct ShadeEnvArgs {
     EnvDev env;
 };
 
+// Multiple importance sampling of lights: what k_shade_mis / k_shade_env_mis read and
+// write beside k_shade's arguments.  The carried record travels with the path state (ping-ponged with the
+// state queues); E is per slot, written at most once per pass (the terminal event ends the path), never
+// L: a shadow trace of the bounce before may still be adding to L[slot] on the side stream.
+struct MisDev {
+    const float4 *carry_in;             // per queue entry: (T.xyz, p_b) of the ray that found this hit; p_b 0: none
+    float4 *carry_out;                  // the same for the extension rays this launch appends
+    const AKR_GLOBAL float *tri_sel;    // per global triangle id: the selection pdf of the light entries naming it
+    float4 *E;                          // per slot: the terminal term (zeroed per pass), added to L by k_splat_mis
+};
+struct ShadeMisArgs {
+    ShadeArgs s;
+    MisDev m;
+};
+struct ShadeEnvMisArgs {
+    ShadeArgs s;
+    EnvDev env;
+    MisDev m;
+};
+
 // The unit entry points (akr_hip_environment_sample / _eval): n inputs (2 floats u, or 3 floats of a
 // world direction) -> world direction (sample only), texel rgb with the scale applied, solid-angle pdf
 struct EnvUnitArgs {
@@ -284,6 +304,12 @@ struct SplatArgs {
     float ray_clamp;
     const uint32_t *order;         // optional: slot of entry i (the cost order) ...
     uint32_t slot_base;            // ... else slot_base + i
+};
+
+// k_splat_mis: k_splat over L + E
+struct SplatMisArgs {
+    SplatArgs s;
+    const float4 *E;
 };
 
 // k_path counting build: per-wave phase profile (wall clock, 100 MHz), summed over waves

@@ -182,4 +182,23 @@ __device__ __forceinline__ V3 closure_sample(const Closure &c, V2 u, V3 wo, V3 &
     return closure_eval(c, wo, wi);
 }
 
+// DiffuseBSDF::evaluate_pdf / MicrofacetReflection::evaluate_pdf (material.h), which the reference's path
+// tracer never calls: the pdf closure_sample draws wi with, without choice_pdf
+__device__ __forceinline__ float closure_pdf(const Closure &c, V3 wo, V3 wi) {
+    if (!same_hemisphere(wo, wi)) return 0.0f;
+    if (c.kind == CL_DIFFUSE) return fabsf(wi.y) * kInvPi;
+    V3 wh = add(wo, wi);
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return 0.0f;
+    wh = normalize(wh);
+    if (wh.y < 0) wh = neg(wh);
+    return ggx_d(c.alpha, wh) * fabsf(wh.y) / (4.0f * fabsf(dot(wo, wh)));
+}
+
+// The power heuristic w(a, b) = 1 / (1 + (b / a)^2), a the pdf of the strategy that drew the direction
+// (a > 0): 0 for b = inf, never 0 / 0
+__device__ __forceinline__ float mis_weight(float a, float b) {
+    const float r = b / a;
+    return 1.0f / (1.0f + r * r);
+}
+
 }  // namespace akr

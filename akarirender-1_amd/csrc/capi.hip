@@ -323,6 +323,28 @@ struct akr_hip_ctx {
         HIPCHK(hipGetLastError());
         return N;
     }
+    // Multiple importance sampling of lights, for sessions started with option "mis": the
+    // carried records (ping-ponged with the state queues), the terminal accumulator of each pass parity and
+    // the per-triangle selection pdf.  mis_on is the option as the session's first call read it.  They are
+    // sized for the session's slots, apart from ensure_capacity's set: growing them moves nothing else.
+    DBuf<float4> d_carry[2], d_E[2];
+    DBuf<float> d_tri_sel;
+    std::vector<float> tri_sel;  // commit_scene: per global triangle id (the sum, if the list names it twice)
+    bool tri_sel_dirty = true;
+    bool mis_on = false;
+    void mis_begin(uint64_t N, hipStream_t st) {
+        mis_on = opt.mis;
+        if (!mis_on || N == 0) return;
+        for (int k = 0; k < 2; k++) {
+            d_carry[k].reserve(N);
+            d_E[k].reserve(N);
+        }
+        if (tri_sel_dirty) {
+            d_tri_sel.upload(tri_sel.data(), tri_sel.size(), st);
+            HIPCHK(hipStreamSynchronize(st));
+            tri_sel_dirty = false;
+        }
+    }
     std::vector<uint32_t> h_pixel;
     bool h_pixel_ok = false;
     DBuf<uint32_t> d_pixel, d_seed, d_slot0, d_slot1, d_counts;
@@ -600,6 +622,12 @@ struct akr_hip_ctx {
         for (size_t i = 0; i < n; i++) ld[i].sel_pdf = func[i] / (func_int * (float)n_lights);  // scene.h:85-89
         d_lights.upload(ld.data(), ld.size(), stream);
         d_cdf.upload(cdf.data(), cdf.size(), stream);
+        // the selection pdf by triangle: what a BSDF-sampled ray that hits a listed triangle
+        // weighs NEE's pdf of the same point with; uploaded when a session starts with option "mis"
+        tri_sel.assign(matid.size(), 0.0f);
+        for (size_t i = 0; i < n; i++)
+            tri_sel[(size_t)mesh_base[lights[i].geom_id] + (size_t)lights[i].prim_id] += ld[i].sel_pdf;
+        tri_sel_dirty = true;
         HIPCHK(hipStreamSynchronize(stream));
         scene_dirty = false;
     }
@@ -1119,6 +1147,7 @@ struct akr_hip_ctx {
         const bool resume = cont && require_session().seeded;  // else every slot starts from x + y * width
         const uint64_t N = cont ? resume_pixels(n_count_words, st) : setup_pixels(tiles, n_tiles, n_count_words, st);
         if (!cont) variance_begin(N, st);  // zeroed on st beside the render; the update follows the join below
+        if (!cont) mis_begin(N, st);       // a continue keeps the session's value
         if (N == 0) return 0;
         if (subset && (!cont || n_subset == 0 || n_subset > N)) throw std::runtime_error("render: invalid slot subset");
         const uint64_t M = subset ? n_subset : N;  // the slots this pass fetches
@@ -1147,7 +1176,8 @@ struct akr_hip_ctx {
                                                        (simple_shading || opt.path_auto_complex));
         // an environment light is shaded by the wavefront's k_shade_env alone, whatever
         // `path` says: the precedent exact_cull and a non-lean view set
-        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_on()) {
+        // and so does option "mis": its kernels are the wavefront's
+        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_on() && !mis_on) {
             if (p.spp > 0) render_path(pass);
             last_passes = 1;
         } else {
@@ -1303,6 +1333,7 @@ struct akr_hip_ctx {
             // L[ps] and the counter set were last used by pass s - 2, whose splat ends its side-stream work
             if (s >= 2) HIPCHK(hipStreamWaitEvent(ms, ev_splat[ps], 0));
             HIPCHK(hipMemsetAsync(cnt, 0, n_count_words * sizeof(uint32_t), ms));
+            if (mis_on) HIPCHK(hipMemsetAsync(d_E[ps].p, 0, N * sizeof(float4), ms));  // like L[ps]: free since pass s - 2
             RaygenArgs rg = raygen_args((uint32_t)M, L, qcount(0), s == 0 && !resume);
             rg.probe = probe_p;
             rg.order = subset ? subset : worder;
@@ -1337,7 +1368,17 @@ struct akr_hip_ctx {
                 sh.max_depth = p.max_depth;
                 sh.last = b == nb - 1;
                 sh.probe = probe_p;
-                if (env_on()) timed("shade", ms, [&] { launch_shade_env(ShadeEnvArgs{sh, env}, (uint32_t)M, ms); });
+                // MIS: the terminal term goes to E[ps], never to L, which the side stream's shadow trace of the
+                // bounce before may be adding to; one queue entry per slot per launch, so E needs no atomic
+                MisDev md{};
+                md.carry_in = odd ? d_carry[1].p : d_carry[0].p;
+                md.carry_out = odd ? d_carry[0].p : d_carry[1].p;
+                md.tri_sel = (decltype(md.tri_sel))d_tri_sel.p;  // device code sees it as a global pointer
+                md.E = d_E[ps].p;
+                if (mis_on && env_on())
+                    timed("shade", ms, [&] { launch_shade_env_mis(ShadeEnvMisArgs{sh, env, md}, (uint32_t)M, ms); });
+                else if (mis_on) timed("shade", ms, [&] { launch_shade_mis(ShadeMisArgs{sh, md}, (uint32_t)M, ms); });
+                else if (env_on()) timed("shade", ms, [&] { launch_shade_env(ShadeEnvArgs{sh, env}, (uint32_t)M, ms); });
                 else timed("shade", ms, [&] { launch_shade(sh, (uint32_t)M, ms); });
                 HIPCHK(hipEventRecord(ev_shade[sq], ms));
                 HIPCHK(hipStreamWaitEvent(side, ev_shade[sq], 0));
@@ -1367,7 +1408,8 @@ struct akr_hip_ctx {
             sp.n = (uint32_t)M;
             sp.ray_clamp = p.ray_clamp;
             sp.order = subset;
-            timed("splat", side, [&] { launch_splat(sp, (uint32_t)M, side); });
+            if (mis_on) timed("splat", side, [&] { launch_splat_mis(SplatMisArgs{sp, d_E[ps].p}, (uint32_t)M, side); });
+            else timed("splat", side, [&] { launch_splat(sp, (uint32_t)M, side); });
             HIPCHK(hipEventRecord(ev_splat[ps], side));
         }
         // the last shade of every pass ran on the main stream and left each slot's sampler state
@@ -2882,6 +2924,7 @@ int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, c
         // the tracker takes the imported film as one batch: P = the film, K = 1 where the weight is positive
         ctx->variance_begin(N, st);
         ctx->variance_update(N, st);
+        ctx->mis_begin(N, st);
         ctx->mark_done(st);
         HIPCHK(hipStreamSynchronize(st));  // the caller's arrays are free again
         ctx->probe_ok = false;

@@ -17,6 +17,10 @@ void launch_splat(const SplatArgs &a, uint32_t max_items, hipStream_t st);
 // with an environment light: k_shade's environment form, and the unit kernels of
 // akr_hip_environment_sample (sample) / akr_hip_environment_eval
 void launch_shade_env(const ShadeEnvArgs &a, uint32_t max_items, hipStream_t st);
+// with multiple importance sampling of lights: the shade kernels' MIS forms and their splat
+void launch_shade_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st);
+void launch_shade_env_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st);
+void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st);
 void launch_env_unit(bool sample, const EnvUnitArgs &a, hipStream_t st);
 void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, uint32_t *gate, hipStream_t st);
 void launch_store_word(const uint32_t *src, uint32_t *dst, hipStream_t st);

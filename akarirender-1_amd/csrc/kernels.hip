@@ -9,6 +9,9 @@
 //   k_shade_env        the same with an environment light: the depth-0 miss sees the
 //                      map, direct lighting samples it
 //   k_splat            Tile::add_sample per pixel, in sample order (core/film.h:66-70)
+//   k_shade_mis, k_shade_env_mis, k_splat_mis
+//                      the same with multiple importance sampling of lights: NEE
+//                      weighted, the BSDF sample's share carried to whatever the extension ray finds
 //
 // Numerics: f32 with the reference's operation order (akr_math.h); the library is built with
 // -ffp-contract=off and correctly rounded division/sqrt.
@@ -1099,10 +1102,24 @@ __device__ __forceinline__ EnvSample env_sample(const EnvDev &e, V2 u, MP mcdf) 
     return s;
 }
 
-template <class Tab, bool ENV = false>
+// Multiple importance sampling: what a hit reads of the ray that found it, and what it
+// hands on.  Only the MIS instantiations of shade_hit_tab touch them.
+struct MisHit {
+    float4 carry;                     // (T, p_b) the ray carries; p_b 0: nothing
+    V3 ro;                            // the ray's origin
+    const AKR_GLOBAL float *tri_sel;  // MisDev::tri_sel
+};
+struct MisOut {
+    bool term;     // the carried pair met a light: E is the terminal term
+    V3 E;
+    float4 carry;  // for the extension ray; .w 0: nothing
+};
+
+template <class Tab, bool ENV = false, bool MIS = false>
 __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab, uint32_t gid, float u, float v, V3 wo,
                                               V3 beta, uint32_t &seed, int depth, int max_depth, bool last, Bounce &o,
-                                              unsigned long long *t_load = nullptr, const EnvDev *env = nullptr) {
+                                              unsigned long long *t_load = nullptr, const EnvDev *env = nullptr,
+                                              const MisHit *mh = nullptr, MisOut *mo = nullptr) {
     o.emit = o.ext = o.sh = false;
     unsigned long long t0 = 0;  // counting builds (t_load): ticks until the shading record is in
     if (t_load) t0 = wall_clock64();
@@ -1134,6 +1151,26 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
                 o.e = mul(beta, mat_rgb(s, mat->color, mat->color_img, tc));
             }
         }
+        if constexpr (MIS) {
+            // the BSDF sample reached an area light: its share of the vertex's direct lighting.  Area and
+            // normal with commit_scene's operations (area_half, lng), so the pdf's bits are the NEE side's
+            if (depth > 0 && mh->carry.w > 0.0f) {
+                const float c = -dot(neg(wo), ng);
+                const V3 po = sub(p, mh->ro);
+                const float d2 = dot(po, po);
+                const V3 lx = cross(sub(v1, v0), sub(v2, v0));
+                const float area_half = sqrtf(dot(lx, lx)) * 0.5f;
+                float sel = mh->tri_sel[gid];
+                if constexpr (ENV) sel = sel * (1.0f - env->select_prob);
+                const float p_l = sel * ((d2 / c) / area_half);
+                // NEE lights front faces only; a triangle outside the light list has sel 0
+                if (c > 0.0f && p_l > 0.0f) {
+                    const V3 T = v3(mh->carry.x, mh->carry.y, mh->carry.z);
+                    mo->term = true;
+                    mo->E = muls(mul(T, mat_rgb(s, mat->color, mat->color_img, tc)), mis_weight(mh->carry.w, p_l));
+                }
+            }
+        }
         return;
     }
     if (depth >= max_depth) return;
@@ -1141,6 +1178,8 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
     uint32_t copy = seed;
     float sel_u = lcg_next(copy);
     float choice_pdf = 1.0f;
+    [[maybe_unused]] bool pair = false;  // MIS: not the last vertex, and not reached through a Mix (whose BSDF draw is the selection's)
+    if constexpr (MIS) pair = !last && mat->type != AKR_MAT_MIX;
     while (mat->type == AKR_MAT_MIX) {  // Material::select_material, material.h:251-268
         const float frac = mat_x(s, mat->frac, mat->frac_img, tc);
         if (sel_u < frac) {
@@ -1171,8 +1210,15 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
     float pdf = 0.0f;
     const V3 f = closure_sample(cl, bu, to_local(frame, wo), wi_l, pdf);
     const V3 wi = to_world(frame, wi_l);
+    [[maybe_unused]] const float p_b = pdf;  // MIS carries closure_sample's value, not a re-evaluation from (wo, wi)
     pdf *= choice_pdf;
     if (pdf == 0.0f) return;
+    if constexpr (MIS) {
+        if (pair && p_b > 0.0f) {  // direct lighting's convention: ns, no choice_pdf
+            const V3 T = divs(mul(beta, muls(f, fabsf(dot(ns, wi)))), p_b);
+            mo->carry = make_float4(T.x, T.y, T.z, p_b);
+        }
+    }
     const float cng = fabsf(dot(ng, wi));
     const V3 ev_beta = divs(muls(f, cng), pdf);
     // select_light(sampler.next2d()) — scene.h:79-90
@@ -1198,6 +1244,10 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
                     o.s0 = make_float4(p.x, p.y, p.z, kEps / fabsf(dot(ng, es.wi)));
                     o.s1 = make_float4(es.wi.x, es.wi.y, es.wi.z, kInf);
                     o.col = col;
+                    if constexpr (MIS)
+                        if (pair)
+                            o.col = muls(col, mis_weight(sel_pdf * es.pdf, closure_pdf(cl, to_local(frame, wo),
+                                                                                       to_local(frame, es.wi))));
                 }
             }
         } else {  // the remap select_material uses
@@ -1237,6 +1287,9 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
                 o.s0 = make_float4(lp.x, lp.y, lp.z, kEps / fabsf(dot(lwi, lng)));
                 o.s1 = make_float4(sdir.x, sdir.y, sdir.z, sqrtf(dist_sqr) * (1.0f - kShadowEps));
                 o.col = col;
+                if constexpr (MIS)
+                    if (pair)
+                        o.col = muls(col, mis_weight(light_pdf, closure_pdf(cl, to_local(frame, wo), to_local(frame, lwi))));
             }
         }
     }
@@ -1258,23 +1311,37 @@ __device__ __forceinline__ void shade_hit(const SceneDev &s, uint32_t gid, float
 #define AKR_SHADE_BLOCK 256
 #endif
 constexpr int kShadeBlock = AKR_SHADE_BLOCK;  // threads per shade workgroup (one queue atomic each)
-template <bool ENV>
-__device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *env) {
+template <bool ENV, bool MIS = false>
+__device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *env, const MisDev *m = nullptr) {
     const uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x;
     const uint32_t n = *a.count_in;
     if (blockIdx.x * kShadeBlock >= n) return;  // whole workgroup past the queue (uniform: before any barrier)
     Bounce bo;
     bo.ext = bo.sh = false;
     uint32_t slot = 0, seed = 0;
+    [[maybe_unused]] MisOut mo;
+    mo.term = false;
+    mo.carry = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (i < n) {
         slot = a.slot_in[i];
         const float4 stv = a.state_in[i];
         seed = fbits(stv.w);
         const float4 hv = a.hit_in[i];
         const uint32_t gid = fbits(hv.w);
+        [[maybe_unused]] MisHit mh;
+        if constexpr (MIS) {  // camera rays carry nothing
+            mh.carry = a.depth > 0 ? m->carry_in[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            mh.tri_sel = m->tri_sel;
+        }
         if (gid != kNoHit) {  // miss -> on_miss (no-op), the path ends
             const float4 rdv = a.ray_in[2 * (size_t)i + 1];
-            if constexpr (ENV)
+            if constexpr (MIS) {
+                const float4 rov = a.ray_in[2 * (size_t)i];
+                mh.ro = v3(rov.x, rov.y, rov.z);
+                shade_hit_tab<GlobalTab, ENV, true>(a.sc, global_tab(a.sc), gid, hv.y, hv.z, neg(v3(rdv.x, rdv.y, rdv.z)),
+                                                    V3{stv.x, stv.y, stv.z}, seed, a.depth, a.max_depth, a.last != 0, bo,
+                                                    nullptr, env, &mh, &mo);
+            } else if constexpr (ENV)
                 shade_hit_tab<GlobalTab, true>(a.sc, global_tab(a.sc), gid, hv.y, hv.z, neg(v3(rdv.x, rdv.y, rdv.z)),
                                                V3{stv.x, stv.y, stv.z}, seed, a.depth, a.max_depth, a.last != 0, bo,
                                                nullptr, env);
@@ -1300,8 +1367,23 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
                 l.y += e.y;
                 l.z += e.z;
                 a.L[slot] = l;
+            } else if constexpr (MIS) {
+                if (mh.carry.w > 0.0f) {  // the BSDF sample reached the environment: its share of direct lighting
+                    const float4 rdv = a.ray_in[2 * (size_t)i + 1];
+                    int ti, tj;
+                    float len;
+                    env_encode(env->n, env_to_map(*env, v3(rdv.x, rdv.y, rdv.z)), ti, tj, len);
+                    const float p_l = (a.sc.n_lights > 0 ? env->select_prob : 1.0f) * env_pdf(*env, ti, tj, len);
+                    if (p_l > 0.0f) {
+                        mo.term = true;
+                        mo.E = muls(mul(v3(mh.carry.x, mh.carry.y, mh.carry.z), env_lookup(*env, ti, tj)),
+                                    mis_weight(mh.carry.w, p_l));
+                    }
+                }
             }
         }
+        if constexpr (MIS)
+            if (mo.term) m->E[slot] = make_float4(mo.E.x, mo.E.y, mo.E.z, 0.0f);  // the path ends here: once per pass
         // the path does not reach another traced bounce: persist its sampler stream for the next
         // sample (the stream continues across spp, cpu/integrator.cpp:124-134)
         if (!bo.ext) a.seed[slot] = seed;
@@ -1319,6 +1401,7 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
         a.ray_out[2 * (size_t)pos + 1] = bo.e1;
         a.state_out[pos] = make_float4(bo.nb.x, bo.nb.y, bo.nb.z, bitsf(seed));
         a.slot_out[pos] = slot;
+        if constexpr (MIS) m->carry_out[pos] = mo.carry;
     }
     if (bo.sh) {  // the shadow trace adds the colour to L[colour.w] when unoccluded
         a.shadow_ray[2 * (size_t)spos] = bo.s0;
@@ -1329,6 +1412,11 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
 __global__ __launch_bounds__(kShadeBlock) void k_shade(ShadeArgs a) { shade_queue<false>(a, nullptr); }
 // with an environment light: the depth-0 miss and the environment's branch of direct lighting
 __global__ __launch_bounds__(kShadeBlock) void k_shade_env(ShadeEnvArgs a) { shade_queue<true>(a.s, &a.env); }
+// with multiple importance sampling of lights: NEE weighted, the BSDF sample's share carried
+__global__ __launch_bounds__(kShadeBlock) void k_shade_mis(ShadeMisArgs a) { shade_queue<false, true>(a.s, nullptr, &a.m); }
+__global__ __launch_bounds__(kShadeBlock) void k_shade_env_mis(ShadeEnvMisArgs a) {
+    shade_queue<true, true>(a.s, &a.env, &a.m);
+}
 
 // the unit entry points: the device functions the shading calls, one input per thread
 __global__ __launch_bounds__(kBlock) void k_env_sample(EnvUnitArgs a) {
@@ -1433,6 +1521,21 @@ __global__ __launch_bounds__(kBlock) void k_splat(SplatArgs a) {
     const uint32_t sl = a.order ? a.order[i] : a.slot_base + i;
     float4 f = a.film[sl];
     splat_one(f, a.L[sl], a.ray_clamp);
+    a.film[sl] = f;
+}
+// the same over L + E: the terminal term is the last of the path's additions
+__global__ __launch_bounds__(kBlock) void k_splat_mis(SplatMisArgs m) {
+    const SplatArgs &a = m.s;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t sl = a.order ? a.order[i] : a.slot_base + i;
+    float4 f = a.film[sl];
+    float4 l = a.L[sl];
+    const float4 e = m.E[sl];
+    l.x += e.x;
+    l.y += e.y;
+    l.z += e.z;
+    splat_one(f, l, a.ray_clamp);
     a.film[sl] = f;
 }
 
@@ -3414,6 +3517,16 @@ void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, 
 void launch_store_word(const uint32_t *src, uint32_t *dst, hipStream_t st) {
     hipLaunchKernelGGL(k_store_word, dim3(1), dim3(64), 0, st, src, dst);
 }
+void launch_shade_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st) {
+    if (max_items == 0) return;
+    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
+    hipLaunchKernelGGL(k_shade_mis, grid, dim3(kShadeBlock), 0, st, a);
+}
+void launch_shade_env_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st) {
+    if (max_items == 0) return;
+    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
+    hipLaunchKernelGGL(k_shade_env_mis, grid, dim3(kShadeBlock), 0, st, a);
+}
 void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st) {
     if (max_items == 0) return;
     hipLaunchKernelGGL(k_ao_shade, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
@@ -3425,6 +3538,10 @@ void launch_ao_resolve(const AoResolveArgs &a, uint32_t max_items, hipStream_t s
 void launch_splat(const SplatArgs &a, uint32_t max_items, hipStream_t st) {
     if (max_items == 0) return;
     hipLaunchKernelGGL(k_splat, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
+}
+void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st) {
+    if (max_items == 0) return;
+    hipLaunchKernelGGL(k_splat_mis, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
 }
 // The persistent path kernel for (kind, count, tab).  The compiler emits the instantiations in the order
 // they are named here, which is the order the code object has always held them in.

@@ -22,6 +22,10 @@ struct Options {
     // slot's mean from its passes (k_variance_update after each call that draws samples).
     // Off: nothing is allocated or launched
     bool film_variance = false;
+    // option "mis" (default 0, read when a session starts): direct lighting is the power-heuristic combination
+    // of the next-event sample and the BSDF sample; the render takes the wavefront form.
+    // Off: nothing is allocated, and every launch is the one it was
+    bool mis = false;
 
     // The render form of a constant-shading scene.  A "tail form"
     // (k_path_spec, or k_path_defer when path_spec is 0) pays where k_path's launch would end on a few
@@ -245,6 +249,11 @@ inline std::string set_option(Options &o, const char *key, int64_t value) {
     if (key && strcmp(key, "film_variance") == 0) {
         if (value != 0 && value != 1) return "film_variance must be in [0, 1]";
         o.film_variance = value == 1;
+        return {};
+    }
+    if (key && strcmp(key, "mis") == 0) {  // the same kind of switch
+        if (value != 0 && value != 1) return "mis must be in [0, 1]";
+        o.mis = value == 1;
         return {};
     }
     const OptionRow *r = find_option(key);

@@ -230,7 +230,12 @@ const char *akr_hip_last_error(const akr_hip_ctx *ctx);
 int akr_hip_set_option(akr_hip_ctx *ctx, const char *key, int64_t value);
 /* One more key is a session switch rather than a knob of the render: "film_variance" (0 or 1, default 0; read when a
  * session starts) makes the session track the variance of every slot's mean from its passes, see
- * akr_hip_render_variance below. */
+ * akr_hip_render_variance below.
+ * And another: "mis" (0 or 1, default 0; read when a session starts, a continue keeps the session's value; any
+ * other value is refused) makes direct lighting the power-heuristic combination of the next-event sample and the
+ * BSDF sample the extension ray already is.  No draw and no ray is added: every slot's sampler
+ * state and ray counts are those of a render without it.  The render takes the wavefront form whatever "path"
+ * says, and akr_hip_render_form reports it.  The AO integrator ignores it. */
 
 int akr_hip_upload_mesh(akr_hip_ctx *ctx, const float *vertices, uint64_t n_vertices,
                         const int32_t *indices, const float *normals, const float *texcoords,
