@@ -255,18 +255,21 @@ __device__ __forceinline__ float ubyte(uint32_t w, int k) {  // v_cvt_f32_ubyte{
 // <= kStackLds), not only while every lane has four free rows.  A slot that is not pushed then writes
 // `dead`, a scratch word of the lane's outside the stack, instead of row sp + 3 (which is row kStackLds
 // or above, past the stack, once sp >= kStackLds - 3).  `info` (counting build): bit 0 the lane pushes
-// or continues, bit 1 sp + 4 > kStackLds, bit 2 sp + pushes > kStackLds.
+// or continues, bit 1 sp + 4 > kStackLds, bit 2 sp + pushes > kStackLds.  `entered` (k_path's product
+// iteration): receives pm, so that the caller tests "no slot entered" on a register of its own instead
+// of on a predicate merged across the visit's branch.
 template <bool ANY, bool NOPOP = false, bool FIT = false>
 __device__ __forceinline__ bool wide_order_push(uint32_t order_lo, uint32_t order_hi, uint32_t dpos, const float (&t)[4],
                                                 const bool (&hit)[4], const uint32_t (&ref)[4], uint32_t &cur, float lim,
                                                 lds_u64 *s_stack, glb_u64 *ovf, uint32_t ovf_threads, uint32_t tid,
                                                 uint32_t gtid, int &sp, lds_u64 *dead = nullptr,
-                                                uint32_t *info = nullptr) {
+                                                uint32_t *info = nullptr, uint32_t *entered = nullptr) {
     const uint32_t perm = ((dpos & 4u) ? order_hi : order_lo) >> ((dpos & 3u) << 3);
     const uint32_t pos[4] = {perm & 3u, (perm >> 2) & 3u, (perm >> 4) & 3u, (perm >> 6) & 3u};
     uint32_t pm = 0;  // entered slots, by position
 #pragma unroll
     for (int k = 0; k < 4; k++) pm |= hit[k] ? (1u << pos[k]) : 0u;
+    if (entered) *entered = pm;
     if (pm == 0) {
         if constexpr (NOPOP) return true;
         cur = stack_pop(s_stack, ovf, ovf_threads, tid, gtid, sp, lim);
@@ -277,7 +280,8 @@ __device__ __forceinline__ bool wide_order_push(uint32_t order_lo, uint32_t orde
         *info = 1u | (sp + 4 > kStackLds ? 2u : 0u) | (sp + (int)__popc(rest) > kStackLds ? 4u : 0u);
     // wave-uniform: no exec-mask split in the common case
     const bool all_lds = FIT ? __ballot(sp + (int)__popc(rest) > kStackLds) == 0 : __ballot(sp + 4 > kStackLds) == 0;
-    if (all_lds) {
+    // FIT: the straight-line push is the fall-through (> 98 % of k_path's pushing iterations)
+    if (FIT ? __builtin_expect(all_lds, 1) : all_lds) {
         // all in LDS: four unconditional writes, no exec-mask branches; a slot that is not pushed
         // writes entry sp + 3, which lies above the new top (sp grows by at most 3) and is dead
         // (FIT: the lane's scratch word)
@@ -383,7 +387,7 @@ __device__ __forceinline__ int visit_wide_lean_node(const WideNode &nd, uint32_t
                                                     float tmin, float tmaxp, float best, lds_u64 *s_stack, glb_u64 *ovf,
                                                     uint32_t ovf_threads, uint32_t tid, uint32_t gtid, int &sp,
                                                     bool *need_pop = nullptr, lds_u64 *dead = nullptr,
-                                                    uint32_t *push_info = nullptr) {
+                                                    uint32_t *push_info = nullptr, uint32_t *entered = nullptr) {
     const float4 h = nd.h;
     const uint4 c = nd.c, qa = nd.qa, qb = nd.qb;
     const uint32_t meta = __float_as_uint(h.w);
@@ -419,7 +423,7 @@ __device__ __forceinline__ int visit_wide_lean_node(const WideNode &nd, uint32_t
     const int tested = (c.x != AKR_CHILD_EMPTY) + (c.y != AKR_CHILD_EMPTY) + (c.z != AKR_CHILD_EMPTY) +
                        (c.w != AKR_CHILD_EMPTY);
     const bool np = wide_order_push<ANY, NOPOP, FIT>(qb.z, qb.w, dpos, t, hit, ref, cur, ANY ? tmaxp : best, s_stack, ovf,
-                                                     ovf_threads, tid, gtid, sp, dead, push_info);
+                                                     ovf_threads, tid, gtid, sp, dead, push_info, entered);
     if (NOPOP) *need_pop = np;
     return tested;
 }
@@ -1646,8 +1650,93 @@ __device__ __forceinline__ void pop_bounded(bool need_pop, PathRay &r, const lds
     if (need_pop) r.cur = got;
 }
 
+// Wave-level sets of k_path's product iteration are carried as 64-bit lane masks.  A mask
+// is only ever taken of a plain register compare (one v_cmp that writes the mask), sets are formed by
+// scalar arithmetic on masks, and a lane reads its bit of a set back as a select condition at no cost.
+// The ballot of a predicate that is itself a combination or was merged across a branch compiles to a
+// v_cndmask 0, 1 / v_cmp_ne pair on this compiler, whose only effect is the AND with EXEC.
+__device__ __forceinline__ unsigned long long mask_of(bool cmp) { return __builtin_amdgcn_ballot_w64(cmp); }
+__device__ __forceinline__ bool in_mask(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// The lanes of a set as a 32-bit scalar (the empty asm keeps the compiler from widening a compare of it to
+// 64 bits, for which there is only a vector instruction)
+__device__ __forceinline__ uint32_t lane_count(unsigned long long m) {
+    uint32_t n = (uint32_t)__popcll(m);
+    asm("" : "+s"(n));
+    return n;
+}
+
+// pop_bounded<false, false> on masks: `need` the popping lanes (each with sp <= kStackLds).  The same
+// rounds, the same entries against the same best, the same r.sp and r.cur.
+__device__ __forceinline__ void pop_bounded_lds(unsigned long long need, PathRay &r, const lds_u64 *s_stack, uint32_t tid,
+                                                uint32_t keep, uint32_t max_rounds) {
+    unsigned long long unserved = need;
+    uint32_t got = AKR_CHILD_POP;
+    int sp = r.sp;
+    uint32_t rounds = 0;
+    while (true) {
+        const unsigned long long has = unserved & mask_of(sp > 0);
+        // every lane reads, a lane that does not pop a row of its own that it ignores
+        const unsigned long long e = lds_get(s_stack, min(max(sp, 1), kStackLds) - 1, tid);
+        const unsigned long long cull = mask_of(__uint_as_float((uint32_t)(e >> 32)) > r.best);
+        got = in_mask(unserved & ~has) ? AKR_CHILD_EMPTY : got;  // nothing left to pop
+        got = in_mask(has & ~cull) ? (uint32_t)e : got;
+        sp -= in_mask(has) ? 1 : 0;
+        unserved = has & cull;
+        rounds++;
+        // one scalar compare and one branch: after the last round no count of unserved lanes reaches the bound
+        if (lane_count(unserved) < (rounds < max_rounds ? keep : 65u)) break;
+    }
+    r.sp = sp;
+    r.cur = in_mask(need) ? got : r.cur;
+}
+
+// k_path's product iteration (path_traverse<false, EXIT, true>): the same visits, pushes, postponements
+// and pops per lane as the general form below, with the wave-level sets as masks.  `bm`: the busy lanes,
+// constant across the call.
+template <int EXIT>
+__device__ __forceinline__ void path_traverse_masks(unsigned long long bm, PathRay &r, const float4 *wn, lds_u64 *s_stack,
+                                                    glb_u64 *ovf, uint32_t ovf_threads, uint32_t tid, uint32_t gtid,
+                                                    uint32_t pop_keep, uint32_t pop_rounds, lds_u64 *dead) {
+    static_assert(EXIT >= 0 && EXIT < 64, "the exit test below counts a searching lane without a holder as 65");
+    PathCount none;
+    while (true) {
+        uint32_t pm = 1u;  // the visit's entered slots; a lane that does not visit enters "one"
+        [[maybe_unused]] bool np;
+        if (in_mask(bm & mask_of(is_internal(r.cur)))) {
+            const WideNode nd = wide_load(wn, r.cur);
+            visit_wide_lean_node<false, true, true>(nd, r.cur, r.o, r.dpos, r.invd, r.tmin, r.tmaxp, r.best, s_stack, ovf,
+                                                    ovf_threads, tid, gtid, r.sp, &np, dead, nullptr, &pm);
+        }
+        // (the empty asm keeps pm a register: the compiler otherwise threads the compare back through the
+        // branch into a merged predicate, whose ballot is the pair above)
+        asm("" : "+v"(pm));
+        unsigned long long need = mask_of(pm == 0);  // the visit entered no slot: pop
+        // the one pop site, for such a visit, for a leaf to postpone and for a pop cut short (see below)
+        const unsigned long long no_leaf = mask_of(r.leaf == AKR_CHILD_EMPTY);
+        const unsigned long long post = bm & ~need & no_leaf & mask_of(is_leaf(r.cur));
+        r.leaf = in_mask(post) ? r.cur : r.leaf;  // postpone the leaf and keep descending
+        need |= post | (bm & mask_of(r.cur == AKR_CHILD_POP));
+        if (need != 0) {
+            if (__builtin_expect((need & mask_of(r.sp > kStackLds)) == 0, 1))
+                pop_bounded_lds(need, r, s_stack, tid, pop_keep, pop_rounds);
+            else
+                pop_bounded<false, true>(in_mask(need), r, s_stack, ovf, ovf_threads, tid, gtid, pop_keep, pop_rounds, none);
+        }
+        const unsigned long long free_now = bm & no_leaf & ~post;  // busy lanes holding no leaf
+        const unsigned long long searching = free_now & mask_of(r.cur != AKR_CHILD_EMPTY);
+        // leave once few lanes still search and some lane holds a leaf, or every ray has finished
+        const unsigned long long holders = bm & ~free_now;
+        // (one scalar compare: without a holder any searching lane counts as 65, above every EXIT)
+        const uint32_t n = lane_count(searching);
+        uint32_t left = holders != 0 ? n : n * 65u;
+        asm("" : "+s"(left));
+        if (left <= (uint32_t)EXIT) break;
+    }
+}
+
 // B. k_trace's traversal phase over every busy lane's ray (all rays here are lean)
-// BOUND (k_path): the pop site runs pop_bounded and the push is wide_order_push's FIT form
+// BOUND (k_path): the pop site runs pop_bounded and the push is wide_order_push's FIT form; the product
+// instantiation runs path_traverse_masks
 template <bool COUNT, int EXIT = kWhileExit, bool BOUND = false>  // EXIT: the phase ends when <= EXIT lanes still search
 __device__ __forceinline__ void path_traverse(bool busy, int kind, PathRay &r, const float4 *wn, lds_u64 *s_stack,
                                               glb_u64 *ovf, uint32_t ovf_threads, uint32_t tid, uint32_t gtid,
@@ -2081,9 +2170,14 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
     V3 beta{1.0f, 1.0f, 1.0f}, Lr{0.0f, 0.0f, 0.0f}, scol{0.0f, 0.0f, 0.0f};
     float4 film = {0.0f, 0.0f, 0.0f, 0.0f};
     float4 pe0 = {}, pe1 = {};  // extension ray waiting behind the shadow ray
-    bool pend = false;
-    bool any = false;           // the lane's ray is a shadow ray (a hit is bgid != kNoHit)
-    bool need_pixel = true, done = false, fin = false, busy = false;
+    // The lane's phase flags, one word across the loop's back edge: as six predicates
+    // the compiler re-merged each of them with the exec mask at every back edge.  A processing phase
+    // unpacks them into locals and packs them again; the phases between read single bits.
+    //   BUSY a ray in flight, DONE no pixel left, FIN a finished ray waits for its processing phase,
+    //   NEED the lane needs a pixel, ANY its ray is a shadow ray (a hit is bgid != kNoHit), PEND an
+    //   extension ray waits behind the shadow ray
+    enum : uint32_t { F_BUSY = 1u, F_DONE = 2u, F_FIN = 4u, F_NEED = 8u, F_ANY = 16u, F_PEND = 32u };
+    uint32_t fl = F_NEED;
     uint32_t pc_closest = 0, pc_shadow = 0;  // counting build: the pixel's rays (akr_pixel_probe)
     PathRay r{};
     r.best = kInf;
@@ -2095,9 +2189,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
 
     while (true) {
         // ---- A. lanes without a ray in flight
-        const unsigned long long waiting = __ballot(!busy && !done);
+        const unsigned long long waiting = mask_of((fl & (F_BUSY | F_DONE)) == 0);
         const uint32_t nwait = (uint32_t)__popcll(waiting);
-        const uint32_t nbusy = (uint32_t)__popcll(__ballot(busy));
+        const uint32_t nbusy = (uint32_t)__popcll(mask_of((fl & F_BUSY) != 0));
         if (nwait == 0 && nbusy == 0) break;
         if (COUNT) {
             p_outer++;
@@ -2109,6 +2203,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 p_procs++;
                 p_lanes += nwait;
             }
+            bool busy = (fl & F_BUSY) != 0, done = (fl & F_DONE) != 0, fin = (fl & F_FIN) != 0;
+            bool need_pixel = (fl & F_NEED) != 0, any = (fl & F_ANY) != 0, pend = (fl & F_PEND) != 0;
             path_park(s_park, tid, r);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             asm volatile("" ::: "memory");
@@ -2238,6 +2334,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 busy = path_begin<COUNT>(a, any, ra, rb, r, s_stack, stack_ovf, tid, gtid, c);
                 fin = !busy;
             }
+            fl = (busy ? F_BUSY : 0u) | (done ? F_DONE : 0u) | (fin ? F_FIN : 0u) | (need_pixel ? F_NEED : 0u) |
+                 (any ? F_ANY : 0u) | (pend ? F_PEND : 0u);
+            asm("" : "+v"(fl));  // stays one register: not six predicates threaded through the phase's branches
             if (COUNT) p_tbegin += wall_clock64() - p_ts;
         }
         if (COUNT) {
@@ -2245,22 +2344,26 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
             p_tp += t - p_t;
             p_t = t;
         }
-        if (!__any(busy)) continue;
+        const unsigned long long bm = mask_of((fl & F_BUSY) != 0);
+        if (bm == 0) continue;
         // ---- B. traversal phase, C. leaf phase (k_trace's, shared with k_path_defer)
-        const int kd = any ? 1 : 0;
-        path_traverse<COUNT, kWhileExitPath, true>(busy, kd, r, a.wide_nodes, s_stack, stack_ovf, a.ovf_threads, tid, gtid,
-                                                   c, pa.pop_keep, pa.pop_rounds, dead);
+        const bool busy = in_mask(bm);
+        const int kd = (fl & F_ANY) != 0 ? 1 : 0;
+        if constexpr (COUNT)
+            path_traverse<COUNT, kWhileExitPath, true>(busy, kd, r, a.wide_nodes, s_stack, stack_ovf, a.ovf_threads, tid,
+                                                       gtid, c, pa.pop_keep, pa.pop_rounds, dead);
+        else
+            path_traverse_masks<kWhileExitPath>(bm, r, a.wide_nodes, s_stack, stack_ovf, a.ovf_threads, tid, gtid,
+                                                pa.pop_keep, pa.pop_rounds, dead);
         if (COUNT) {
             const unsigned long long t = wall_clock64();
             p_tt += t - p_t;
             p_t = t;
         }
         const bool hit_any = path_leaf<COUNT>(busy, kd, r, a.wide_leaves, c);
-        if (busy && (hit_any || r.cur == AKR_CHILD_EMPTY)) {
-            busy = false;
-            fin = true;
-            if (COUNT) c.deep[kd] += c.deep_now ? 1 : 0;
-        }
+        const bool ended = busy && (hit_any || r.cur == AKR_CHILD_EMPTY);
+        fl = ended ? (fl ^ (F_BUSY | F_FIN)) : fl;  // busy and not fin before: the ray waits for its processing phase
+        if (COUNT && ended) c.deep[kd] += c.deep_now ? 1 : 0;
         if (COUNT) p_tl += wall_clock64() - p_t;
     }
     if (COUNT) {
