@@ -23,6 +23,7 @@
 #include "bvh_build.h"
 #include "kernels.h"
 #include "options.h"
+#include "leaf_layout.h"
 #include "path_plan.h"
 
 using namespace akr;
@@ -195,6 +196,7 @@ struct akr_hip_ctx {
     DBuf<akr_bvh4_node> d_wnodes;
     DBuf<float4> d_wleaves;          // leaf blob (see TraceArgs::wide_leaves)
     uint32_t wide_root_dev = AKR_CHILD_EMPTY;
+    bool leaf_one_kernel = false;  // k_path's one-triangle leaf phase pays on this tree (leaf_layout.h leaf_one_pays)
     uint64_t bvh_dev_bytes = 0;       // the uploaded wide nodes + leaf blob
     DBuf<float4> d_tris;
     DBuf<ShadeTri> d_shade_tri;
@@ -829,7 +831,7 @@ struct akr_hip_ctx {
         pp.state_in = pp.state_out = nullptr;
         const uint32_t grid = (uint32_t)std::max<uint64_t>(
             1, std::min<uint64_t>(path_grid[PATH_PLAIN][tab], ((uint64_t)N + kTraceBlock - 1) / kTraceBlock));
-        launch_path(true, PATH_PLAIN, tab, pp, grid, ms);
+        launch_path(true, PATH_PLAIN, tab, leaf_one_kernel, pp, grid, ms);
         HIPCHK(hipMemsetAsync(d_film.p, 0, (size_t)N * sizeof(float4), ms));
     }
 
@@ -1287,7 +1289,7 @@ struct akr_hip_ctx {
             }
         }
         timed("path", ms, [&] {  // one timed record: a gated launch that exits at once adds microseconds
-            for (int k = 0; k < pl.n_launch; k++) launch_path(opt.count, pl.launch[k].kind, tab, args[k], pl.launch[k].grid, ms);
+            for (int k = 0; k < pl.n_launch; k++) launch_path(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, args[k], pl.launch[k].grid, ms);
         });
         HIPCHK(hipGetLastError());
         form_pending = pl.gated;
@@ -1991,26 +1993,20 @@ void finish_accel(akr_hip_ctx *ctx, int n_threads) {
         // Offsets by a serial prefix sum, then the records and their triangles are copied on
         // `n_threads` threads (the blob is ~1 GB on C3).
         const auto &leaves = ctx->bvh4.leaves;
-        std::vector<uint32_t> leaf_off(leaves.size());
-        size_t words = 0;
-        const size_t align = (size_t)std::max(1, ctx->opt.leaf_align);
-        for (size_t i = 0; i < leaves.size(); i++) {
-            words = (words + align - 1) / align * align;
-            if (words >= AKR_CHILD_LEAF) break;
-            leaf_off[i] = (uint32_t)words;
-            words += 2 + 3 * (size_t)leaves[i].count;
-        }
-        if (words >= AKR_CHILD_LEAF) throw std::runtime_error("BVH too large for the wide leaf blob");
-        // zero float4 of padding behind the last leaf: a leaf phase fetches the second triangle
-        // record with the header whatever the leaf's count (kernels.hip path_leaf)
-        const size_t pad = 3;
+        // (leaf_layout.h: the offsets, the size check and the references' one-triangle flag)
+        const akr::LeafLayout lay = akr::leaf_layout(leaves.size(), (size_t)std::max(1, ctx->opt.leaf_align),
+                                                     [&](size_t i) { return leaves[i].count; });
+        const std::vector<uint32_t> &leaf_off = lay.offset;
+        const size_t words = lay.words, pad = akr::kLeafBlobPad, align = (size_t)std::max(1, ctx->opt.leaf_align);
         std::unique_ptr<float4[]> blob(new float4[words + pad]);
         if (align > 1) std::memset(static_cast<void *>(blob.get()), 0, sizeof(float4) * (words + pad));  // the gaps
         else std::memset(static_cast<void *>(blob.get() + words), 0, sizeof(float4) * pad);
         const float4 *tri4 = reinterpret_cast<const float4 *>(b.tris.data());
         std::vector<akr_bvh4_node> wn = ctx->bvh4.nodes;
         auto remap = [&](uint32_t r) {
-            return (r != AKR_CHILD_EMPTY && (r & AKR_CHILD_LEAF)) ? (AKR_CHILD_LEAF | leaf_off[r & 0x7FFFFFFFu]) : r;
+            if (r == AKR_CHILD_EMPTY || !(r & AKR_CHILD_LEAF)) return r;
+            const uint32_t i = r & 0x7FFFFFFFu;
+            return lay.ref(i, leaves[i].count);
         };
         const int nt = n_threads > 0 ? std::min(n_threads, 64)
                                        : (int)std::min(64u, std::max(1u, std::thread::hardware_concurrency()));
@@ -2035,6 +2031,9 @@ void finish_accel(akr_hip_ctx *ctx, int n_threads) {
         };
         run_on_threads(nt, fill);
         ctx->wide_root_dev = remap(ctx->bvh4.root_ref);
+        size_t n_one = 0;
+        for (const akr_bvh_leaf &l : leaves) n_one += l.count == 1 ? 1 : 0;
+        ctx->leaf_one_kernel = akr::leaf_one_pays(n_one, leaves.size());
         ctx->d_wnodes.reserve(1);  // never a null pointer, even for an empty scene
         ctx->d_wleaves.reserve(1);
         ctx->d_wnodes.upload(wn.data(), wn.size(), ctx->stream);

@@ -27,7 +27,8 @@ void launch_store_word(const uint32_t *src, uint32_t *dst, hipStream_t st);
 void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st);
 void launch_ao_resolve(const AoResolveArgs &a, uint32_t max_items, hipStream_t st);
 // persistent path kernel forms: PATH_PLAIN / PATH_DEFER / PATH_SPEC (akr_path_forms.h)
-void launch_path(bool count, int kind, bool tab, const PathArgs &a, uint32_t grid, hipStream_t st);
+// leaf_one: PATH_PLAIN's product build with the one-triangle leaf phase (k_path) or without (k_path_general)
+void launch_path(bool count, int kind, bool tab, bool leaf_one, const PathArgs &a, uint32_t grid, hipStream_t st);
 int path_blocks_per_cu(int kind, bool tab);
 bool path_tab_fits(int32_t n_mats, int32_t n_lights);
 void launch_check_weights(const float4 *film, uint32_t n, float expect, uint32_t *bad, hipStream_t st);

@@ -18,6 +18,7 @@
 #include "akr_device.h"
 #include "akr_math.h"
 #include "kernels.h"
+#include "leaf_layout.h"
 
 namespace akr {
 
@@ -717,7 +718,7 @@ __global__ __launch_bounds__(kTraceBlock) AKR_TRACE_ATTR void k_trace(TraceArgs 
                 float4 pa, pb, pc;     // the first one, fetched together with the leaf header
                 float4 pa1, pb1, pc1;  // and the second one (wide view only: its blob is padded)
                 if (WIDE) {  // the leaf's exact box, with the current best: the BVH2 pop-time test
-                    const float4 *lr = a.wide_leaves + (leaf & 0x7FFFFFFFu);
+                    const float4 *lr = a.wide_leaves + (leaf & kLeafOffsetMask);
                     const float4 l0 = lr[0], l1 = lr[1];  // lo.xyz hi.x | hi.yz first count
                     pa = lr[2];
                     pb = lr[3];
@@ -1876,7 +1877,7 @@ __device__ __forceinline__ bool path_leaf(bool busy, int kind, PathRay &r, const
                              // allocates the persistent kernels' registers differently)
         bool hit_any = false;
         if (busy && r.leaf != AKR_CHILD_EMPTY) {
-            const float4 *lr = wide_leaves + (r.leaf & 0x7FFFFFFFu);
+            const float4 *lr = wide_leaves + (r.leaf & kLeafOffsetMask);
             const float4 l0 = lr[0], l1 = lr[1];
             const float4 pa0 = lr[2], pb0 = lr[3], pc0 = lr[4];
             const float4 pa1 = lr[5], pb1 = lr[6], pc1 = lr[7];
@@ -1912,7 +1913,7 @@ __device__ __forceinline__ bool path_leaf(bool busy, int kind, PathRay &r, const
         c.lphases += holders ? 1u : 0u;
         c.lholders += holders;
         // every lane loads (a lane without a leaf the blob's first record: see path_traverse)
-        const float4 *lr = wide_leaves + (in_leaf ? (r.leaf & 0x7FFFFFFFu) : 0u);
+        const float4 *lr = wide_leaves + (in_leaf ? (r.leaf & kLeafOffsetMask) : 0u);
         const float4 l0 = lr[0], l1 = lr[1], pa0 = lr[2], pb0 = lr[3], pc0 = lr[4], pa1 = lr[5], pb1 = lr[6],
                      pc1 = lr[7];
         const unsigned long long tb = wall_clock64();
@@ -1925,6 +1926,61 @@ __device__ __forceinline__ bool path_leaf(bool busy, int kind, PathRay &r, const
         c.tl_comp += wall_clock64() - tc;
         return hit_any;
     }
+}
+
+// k_path's product leaf phase, on masks as path_traverse_masks: `bm` the busy lanes, `am`
+// the lanes whose ray is an occlusion ray; returns the lanes whose occlusion ray found its first hit.
+// When every pending leaf of the wave holds one triangle (its reference says so: kLeafOne), the phase is
+// one straight-line block: the header and the one record in a batch of five loads, the exact box,
+// mt()'s operations in mt()'s order for every holder, and the outcome as scalar arithmetic on the masks of
+// the very compares that mt() and path_leaf() branch on, so a NaN decides what it decides there.  A lane
+// that mt() would have left early computes values nobody reads (f32 arithmetic does not trap).  A wave
+// with a leaf of several triangles among its holders (about 1 % of the phases on the C3 soup) runs
+// path_leaf()'s general form.  The two are consecutive conditional blocks, not the arms of one branch:
+// as arms, the register allocator copied best, bu, bv, bgid and the leaf out and back around the phase.
+// (The block's record 0 exists: a holder with the flag means the blob holds a leaf of 5 float4.)
+__device__ __forceinline__ unsigned long long path_leaf_masks(unsigned long long bm, unsigned long long am, PathRay &r,
+                                                              const float4 *wide_leaves) {
+    // (AKR_CHILD_EMPTY carries the bit too: only a holder's says anything)
+    const unsigned long long hold = bm & mask_of(r.leaf != AKR_CHILD_EMPTY);
+    const unsigned long long one = hold & mask_of((r.leaf & kLeafOne) != 0);
+    unsigned long long hm = 0;
+    const bool several = hold != one;  // some holder's leaf holds more: the whole wave takes the general form
+    if (__builtin_expect(one != 0 && !several, 1)) {
+        // every lane loads, a lane outside `one` the blob's first record, which it ignores: no exec region
+        const float4 *lr = wide_leaves + (in_mask(one) ? (r.leaf & kLeafOffsetMask) : 0u);
+        const float4 l0 = lr[0], l1 = lr[1];
+        const float4 a = lr[2], b = lr[3], c = lr[4];
+        const float tl = box_test<true, true>(l0.x, l0.w, l0.y, l1.x, l0.z, l1.y, r.o, r.invd, r.tmin, r.tmax);
+        const unsigned long long out = mask_of(tl < 0.0f) | mask_of(tl > r.best);  // in = !(tl < 0 || tl > best)
+        // mt(r.o, r.d, r.tmin, r.tmax, a, b, c, r.best, t, u, v)
+        const V3 v0{a.x, a.y, a.z}, e1{b.x, b.y, b.z}, e2{c.x, c.y, c.z};
+        const V3 h = cross(r.d, e2);
+        const float det = dot(e1, h);
+        const unsigned long long flat = mask_of(det > -1e-6f) & mask_of(det < 1e-6f);
+        const float f = 1.0f / det;
+        const V3 s = sub(r.o, v0);
+        const float u = f * dot(s, h);
+        const unsigned long long out_u = mask_of(u < 0.0f) | mask_of(u > 1.0f);
+        const V3 q = cross(s, e1);
+        const float v = f * dot(r.d, q);
+        const unsigned long long out_v = mask_of(v < 0.0f) | mask_of(u + v > 1.0f);
+        const float t = f * dot(e2, q);
+        const unsigned long long near = mask_of(t > r.tmin) & mask_of(t < r.tmax) & mask_of(t < r.best);
+        const unsigned long long hit = one & near & ~(out | flat | out_u | out_v);
+        const bool won = in_mask(hit);
+        r.best = won ? t : r.best;
+        r.bu = won ? u : r.bu;
+        r.bv = won ? v : r.bv;
+        r.bgid = won ? fbits(a.w) : r.bgid;
+        r.leaf = in_mask(one) ? AKR_CHILD_EMPTY : r.leaf;
+        hm = hit & am;
+    }
+    if (__builtin_expect(several, 0)) {
+        PathCount none{};  // (the product build of path_leaf tallies nothing)
+        hm |= mask_of(path_leaf<false>(in_mask(bm), in_mask(am) ? 1 : 0, r, wide_leaves, none));
+    }
+    return hm;
 }
 
 // A fresh ray into the traversal state: lean rays enter the loop (returns true: the lane is busy),
@@ -2133,8 +2189,10 @@ __device__ __forceinline__ uint32_t probe_flags(const PathArgs &pa) {
 
 constexpr int kParkSlots = 8;
 
-template <bool COUNT, bool TAB>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path(PathArgs pa) {
+// ONE: the product leaf phase is path_leaf_masks (k_path); else path_leaf's general form for every wave
+// (k_path_general, the kernel of scenes whose leaves mostly hold several triangles: leaf_layout.h leaf_one_pays)
+template <bool COUNT, bool TAB, bool ONE>
+__device__ __forceinline__ void path_plain(const PathArgs &pa) {
     if (pa.gate && *pa.gate != pa.gate_want) return;  // the other candidate form runs (uniform: before any barrier)
     const TraceArgs &a = pa.t;
     __shared__ unsigned long long s_stack_mem[kStackLdsU64];
@@ -2348,7 +2406,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
         if (bm == 0) continue;
         // ---- B. traversal phase, C. leaf phase (k_trace's, shared with k_path_defer)
         const bool busy = in_mask(bm);
-        const int kd = (fl & F_ANY) != 0 ? 1 : 0;
+        [[maybe_unused]] const int kd = (fl & F_ANY) != 0 ? 1 : 0;
         if constexpr (COUNT)
             path_traverse<COUNT, kWhileExitPath, true>(busy, kd, r, a.wide_nodes, s_stack, stack_ovf, a.ovf_threads, tid,
                                                        gtid, c, pa.pop_keep, pa.pop_rounds, dead);
@@ -2360,8 +2418,14 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
             p_tt += t - p_t;
             p_t = t;
         }
-        const bool hit_any = path_leaf<COUNT>(busy, kd, r, a.wide_leaves, c);
-        const bool ended = busy && (hit_any || r.cur == AKR_CHILD_EMPTY);
+        bool ended;
+        if constexpr (COUNT || !ONE) {
+            const bool hit_any = path_leaf<COUNT>(busy, kd, r, a.wide_leaves, c);
+            ended = busy && (hit_any || r.cur == AKR_CHILD_EMPTY);
+        } else {
+            const unsigned long long hm = path_leaf_masks(bm, mask_of((fl & F_ANY) != 0), r, a.wide_leaves);
+            ended = in_mask(bm & (hm | mask_of(r.cur == AKR_CHILD_EMPTY)));
+        }
         fl = ended ? (fl ^ (F_BUSY | F_FIN)) : fl;  // busy and not fin before: the ray waits for its processing phase
         if (COUNT && ended) c.deep[kd] += c.deep_now ? 1 : 0;
         if (COUNT) p_tl += wall_clock64() - p_t;
@@ -2375,6 +2439,15 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
             atomicAdd(&pa.prof->tp_load, p_tload);
         }
     }
+}
+
+template <bool COUNT, bool TAB>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path(PathArgs pa) {
+    path_plain<COUNT, TAB, true>(pa);
+}
+template <bool TAB>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_general(PathArgs pa) {
+    path_plain<false, TAB, false>(pa);
 }
 
 __device__ __forceinline__ void path_park(uint32_t (*s_park)[kTraceBlock], uint32_t tid, const PathRay &r) {
@@ -3649,7 +3722,7 @@ void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st)
 // The persistent path kernel for (kind, count, tab).  The compiler emits the instantiations in the order
 // they are named here, which is the order the code object has always held them in.
 using PathKernel = void (*)(PathArgs);
-static PathKernel path_kernel(int kind, bool count, bool tab) {
+static PathKernel path_kernel(int kind, bool count, bool tab, bool leaf_one = true) {
     if (count && tab) {
         if (kind == PATH_DEFER) return k_path_defer<true, true>;
         if (kind == PATH_SPEC) return k_path_spec<true, true>;
@@ -3662,12 +3735,13 @@ static PathKernel path_kernel(int kind, bool count, bool tab) {
     }
     if (kind == PATH_SPEC) return tab ? k_path_spec<false, true> : k_path_spec<false, false>;
     if (kind == PATH_DEFER) return tab ? k_path_defer<false, true> : k_path_defer<false, false>;
+    if (!leaf_one) return tab ? k_path_general<true> : k_path_general<false>;
     return tab ? k_path<false, true> : k_path<false, false>;
 }
-void launch_path(bool count, int kind, bool tab, const PathArgs &a, uint32_t grid, hipStream_t st) {
+void launch_path(bool count, int kind, bool tab, bool leaf_one, const PathArgs &a, uint32_t grid, hipStream_t st) {
     if (grid == 0) return;
     if (tab && !path_tab_fits(a.sc.n_mats, a.sc.n_lights)) tab = false;  // the LDS copy must hold every record
-    hipLaunchKernelGGL(path_kernel(kind, count, tab), dim3(grid), dim3(kTraceBlock), 0, st, a);
+    hipLaunchKernelGGL(path_kernel(kind, count, tab, leaf_one), dim3(grid), dim3(kTraceBlock), 0, st, a);
 }
 int path_blocks_per_cu(int kind, bool tab) {
     int nb = 0;
