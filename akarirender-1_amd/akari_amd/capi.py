@@ -174,6 +174,7 @@ EXPORTS = {
     "akr_hip_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "akr_hip_upload_mesh": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, C.c_uint64, _P, C.c_int32,
                                       C.POINTER(C.c_int32)]),
+    "akr_hip_clear_meshes": (C.c_int, [_P]),
     "akr_hip_upload_images": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "akr_hip_upload_textures": (C.c_int, [_P, _P, C.c_int32]),
     "akr_hip_upload_materials": (C.c_int, [_P, _P, C.c_int32]),
@@ -404,6 +405,10 @@ class HipContext:
         self._check(self.lib.akr_hip_upload_mesh(self.h, _ptr(v), v.size // 3, _ptr(i), _ptr(n), _ptr(t), _ptr(m),
                                                  nt, _ptr(s), s.size, C.byref(gid)))
         return gid.value
+
+    def clear_meshes(self):
+        """Forget every uploaded mesh (upload_mesh appends) and the tree built over them."""
+        self._check(self.lib.akr_hip_clear_meshes(self.h))
 
     def upload_textures(self, texs):
         arr = (Texture * max(1, len(texs)))(*texs)

@@ -408,6 +408,8 @@ int validate_bvh2(const akr_bvh_node *nodes, uint64_t n_nodes, const akr_bvh_tri
         if (r & AKR_CHILD_LEAF) {
             const uint64_t first = akr_leaf_first(r), cnt = akr_leaf_count(r);
             if (cnt > AKR_LEAF_MAX || first + cnt > n_tris) throw std::runtime_error("BVH: leaf outside the triangles");
+            // the depth counts leaves (as build_lbvh_gpu's and the host builders' max_depth do)
+            if (d > AKR_BVH_MAX_DEPTH) throw std::runtime_error("BVH: deeper than AKR_BVH_MAX_DEPTH");
             max_leaf = std::max(max_leaf, (int)cnt);
             depth = std::max(depth, d);
             return;

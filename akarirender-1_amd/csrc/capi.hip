@@ -1755,6 +1755,20 @@ int akr_hip_upload_mesh(akr_hip_ctx *ctx, const float *vertices, uint64_t n_vert
     });
 }
 
+int akr_hip_clear_meshes(akr_hip_ctx *ctx) {
+    return guard(ctx, [&] {
+        ctx->verts.clear();
+        ctx->idx.clear();
+        ctx->normals.clear();
+        ctx->texcoords.clear();
+        ctx->matid.clear();
+        ctx->mesh_base.assign(1, 0u);
+        ctx->scene_dirty = true;
+        ctx->drop_session();
+        ctx->accel_built = false;
+    });
+}
+
 int akr_hip_upload_images(akr_hip_ctx *ctx, const float *rgba, const int32_t *widths, const int32_t *heights,
                           int32_t n_images) {
     return guard(ctx, [&] {

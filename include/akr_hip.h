@@ -241,6 +241,10 @@ int akr_hip_upload_mesh(akr_hip_ctx *ctx, const float *vertices, uint64_t n_vert
                         const int32_t *indices, const float *normals, const float *texcoords,
                         const int32_t *material_indices, uint64_t n_triangles,
                         const int32_t *material_slots, int32_t n_slots, int32_t *geom_id);
+/* akr_hip_upload_mesh appends: geom_id counts the meshes the context holds.  This forgets them all (and the
+ * acceleration structure built over them), so that the context can take another scene's meshes from
+ * geom_id 0; textures, materials, lights, environment and camera stay as they were uploaded. */
+int akr_hip_clear_meshes(akr_hip_ctx *ctx);
 int akr_hip_upload_images(akr_hip_ctx *ctx, const float *rgba, const int32_t *widths,
                           const int32_t *heights, int32_t n_images);
 int akr_hip_upload_textures(akr_hip_ctx *ctx, const akr_texture *textures, int32_t n);
@@ -333,7 +337,7 @@ int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const a
  *
  *  - akr_hip_render and akr_hip_render_device start a new session (replacing any earlier one), and so
  *    does akr_hip_render_state_import.  A continue extends the session.
- *  - akr_hip_upload_mesh / _images / _textures / _materials / _lights, akr_hip_build_accel,
+ *  - akr_hip_upload_mesh / _images / _textures / _materials / _lights, akr_hip_clear_meshes, akr_hip_build_accel,
  *    akr_hip_import_accel, akr_hip_set_camera, akr_hip_render_ao, and akr_hip_render_node on a member
  *    context end it.  A continue without a session returns a non-zero status whose message begins
  *    "no render session to continue"; the context stays usable.  A continue that fails while

@@ -42,6 +42,239 @@ def small_soup(n_tris=20000, resolution=(96, 54), seed=42, r=0.01):
     return scene.soup_scene(n_tris=n_tris, resolution=resolution, seed=seed, r=r)
 
 
+def tri_scene(tris, mats, mat_ids, cam):
+    """One mesh of unshared-vertex triangles [n, 3, 3] with their geometric normals (up where a
+    triangle has no area)."""
+    tris = np.asarray(tris, np.float32).reshape(-1, 3, 3)
+    n = len(tris)
+    t64 = tris.astype(np.float64)
+    nrm = np.cross(t64[:, 1] - t64[:, 0], t64[:, 2] - t64[:, 0])
+    length = np.linalg.norm(nrm, axis=1, keepdims=True)
+    nrm = np.where(length > 1e-20, nrm / np.maximum(length, 1e-20), np.array([0.0, 1.0, 0.0]))
+    mesh = scene.Mesh(tris.reshape(-1, 3), np.arange(3 * n, dtype=np.int32).reshape(-1, 3),
+                      np.repeat(nrm.astype(np.float32), 3, axis=0).reshape(n, 9),
+                      np.tile(np.array([0, 0, 1, 0, 0, 1], np.float32), (n, 1)), np.asarray(mat_ids, np.int32), mats)
+    return scene.Scene(camera=cam, shapes=[mesh])
+
+
+def _grey_and_light():
+    ct = scene.ConstantTexture
+    return [scene.DiffuseMaterial(ct([0.6, 0.55, 0.5])), scene.EmissiveMaterial(ct([10.0, 10.0, 10.0]), double_sided=True)]
+
+
+_CAM = dict(position=(0.0, 0.0, 4.0), rotation=(0.0, 0.0, 0.0), fov=40.0, resolution=(24, 24))
+
+
+def soup_total(total, resolution=(24, 24), seed=42):
+    """The seeded soup with `total` triangles in all, its two-triangle light quad included; below
+    three triangles, the first `total` of the one-triangle soup and its quad."""
+    sc = small_soup(max(total - 2, 1), resolution, seed)
+    if total < 3:
+        m = sc.shapes[0]
+        m.vertices, m.indices = m.vertices[:3 * total], m.indices[:total]
+        m.normals, m.texcoords, m.material_indices = m.normals[:total], m.texcoords[:total], m.material_indices[:total]
+    assert sc.shapes[0].n_tris == total
+    return sc
+
+
+def shifted_soup(total=1000, offset=(-1000.0, 2000.0, 0.5)):
+    """The `total`-triangle soup moved far from the origin: negative and large coordinates, centres
+    whose low bits are lost, a scene bound that cancels in c - lo."""
+    sc = soup_total(total)
+    m = sc.shapes[0]
+    m.vertices = (np.asarray(m.vertices, np.float32) + np.asarray(offset, np.float32)).astype(np.float32)
+    return sc
+
+
+def duplicates_soup():
+    """The 500-triangle soup (and its quad) with triangles 100..199 made copies of triangle 0."""
+    sc = small_soup(500)
+    m = sc.shapes[0]
+    m.vertices[3 * 100:3 * 200] = np.tile(m.vertices[0:3], (100, 1))
+    return sc
+
+
+def sheet_scene(quads=16):
+    """quads x quads squares, two triangles each, in the plane z = 0: no extent along z."""
+    tris = []
+    for y in range(quads):
+        for x in range(quads):
+            a, b, c, d = (x, y, 0.0), (x + 1, y, 0.0), (x + 1, y + 1, 0.0), (x, y + 1, 0.0)
+            tris += [[a, b, c], [a, c, d]]
+    return tri_scene(np.array(tris, np.float32) / np.float32(quads), _grey_and_light(), [0] * len(tris),
+                     scene.PerspectiveCamera(**_CAM))
+
+
+def identical_scene(n=300):
+    """n copies of one triangle: one Morton code, a tree built from sorted positions alone."""
+    tri = [(0.25, -0.5, 0.125), (1.0, 0.75, -0.25), (-0.5, 0.5, 0.5)]
+    return tri_scene(np.array([tri] * n, np.float32), _grey_and_light(), [0] * n, scene.PerspectiveCamera(**_CAM))
+
+
+def signed_zero_pair():
+    """Two triangles in planes x = -0.0 and x = +0.0 (every x coordinate carries its triangle's sign
+    of zero, so the centres' x are -0.0 and +0.0) whose centres differ along y."""
+    nz, pz = np.float32(-0.0), np.float32(0.0)
+    tris = np.array([[(pz, 2.0, 0.0), (pz, 3.0, 0.0), (pz, 2.0, 1.0)],
+                     [(nz, 0.0, 0.0), (nz, 1.0, 0.0), (nz, 0.0, 1.0)]], np.float32)
+    assert np.signbit(tris[1, :, 0]).all() and not np.signbit(tris[0, :, 0]).any()
+    return tri_scene(tris, _grey_and_light(), [0, 0], scene.PerspectiveCamera(**_CAM))
+
+
+CHAIN_CELLS = 2097151   # 2^21 - 1, the builder's largest cell index
+
+
+def chain_cells(n_tris=65):
+    """The cells [n, 3] the chain scene's triangles are meant to fall in."""
+    cells = np.zeros((n_tris, 3), np.int64)
+    for j in range(63):
+        cells[j, j % 3] = 1 << (20 - j // 3)
+    cells[64] = CHAIN_CELLS
+    return cells
+
+
+def _chain_geometry(n_tris):
+    """(centres, half-extents) of the chain scene's triangles in world units."""
+    cells = chain_cells(65).astype(np.float64)
+    centre = np.where((cells > 0) & (cells < CHAIN_CELLS), cells + 0.5, cells)
+    half = np.maximum(0.25, cells.max(axis=1) / 4.0)
+    half[64] = 2.0 ** 19
+    if n_tris == 66:
+        centre, half = np.concatenate([centre, centre[63:64]]), np.concatenate([half, half[63:64]])
+    return centre * CHAIN_UNIT, half * CHAIN_UNIT
+
+
+CHAIN_UNIT = 2.0 ** -20    # world units per cell: a power of two, so every quotient (c - lo) / ext is the cells' own
+_CHAIN_CORNERS = np.array([(-1, -1, -1), (1, 1, -1), (-1, 1, 1)], np.float64)      # spans [-h, h] on every axis
+
+
+def chain_scene(n_tris=65, resolution=(24, 24)):
+    """The deepest tree the LBVH builder accepts.  In units of one cell (2^-20 world units, the scene
+    spanning [0, 2) like the other test scenes): triangle j < 63 has its box centre at
+    2^(20 - j // 3) + 0.5 on axis j % 3 and at 0 on the other two, so its Morton code is the single bit
+    62 - j; triangle 63 is centred at the origin (code 0) and triangle 64, the light, at 2097151 on every
+    axis (all 63 bits), which makes the scene bounds of the centres [0, 2097151]^3.  Sorted, the codes are
+    0, 2^0, ..., 2^62, 2^63 - 1: below the root every split peels one triangle off the top of what is
+    left, a chain.  With 65 triangles the tree has 64 levels (leaves counted); with 66, a copy of
+    triangle 63 appended, the bottom leaf becomes a node: 65 levels.  Every triangle's half-extent is a
+    power of two that keeps centre - h and centre + h exact in f32, so 0.5 * mn + 0.5 * mx is the centre
+    exactly; the triangles grow with their distance from the origin so that the camera sees some."""
+    assert n_tris in (65, 66)
+    centre, half = _chain_geometry(n_tris)
+    tris = centre[:, None, :] + half[:, None, None] * _CHAIN_CORNERS[None]
+    assert np.array_equal(tris.astype(np.float32).astype(np.float64), tris)   # every coordinate exact in f32
+    tris[64] = tris[64][[0, 2, 1]]             # the light's front (its next-event sampling is one-sided) towards the chain
+    mat_ids = [0] * n_tris
+    mat_ids[64] = 1
+    cam = scene.PerspectiveCamera(position=(0.0, 0.0, 4.0), rotation=(0.0, 0.0, 0.0), fov=60.0,
+                                  resolution=tuple(resolution))
+    return tri_scene(tris, _grey_and_light(), mat_ids, cam)
+
+
+def chain_rays(seed=3):
+    """Rays for the chain scene: along its diagonal in both directions (through the origin triangle
+    and the far one, inside every box of the chain), jittered copies of them, and rays aimed at the
+    centroid of every triangle from points around the scene."""
+    rng = np.random.default_rng(seed)
+    centre, half = _chain_geometry(65)
+    centroid = centre + half[:, None] * _CHAIN_CORNERS.mean(axis=0)
+    diag = np.ones(3) / np.sqrt(3.0)
+    o = [-0.1 * np.ones(3), 3.0 * np.ones(3)] + [-0.1 * np.ones(3) + 1e-6 * rng.normal(size=3) for _ in range(64)]
+    d = [diag, -diag] + [diag + 1e-6 * rng.normal(size=3) for _ in range(64)]
+    for t, h in zip(centroid, half):
+        for _ in range(16):
+            p = rng.uniform(-1.0, 3.0, 3)
+            o.append(p)
+            d.append(t + rng.normal(size=3) * 0.05 * h - p)
+    d = np.array(d)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    r = np.zeros(len(o), capi.RAY_DTYPE)
+    r["o"], r["d"] = np.array(o, np.float32), d.astype(np.float32)
+    r["tmin"], r["tmax"] = np.float32(1e-3), np.float32(np.inf)
+    return r
+
+
+def chain_axis_rays():
+    """Three rays from beside the chain scene's origin, each a hair off one axis (every 1 / d finite, so
+    they stay in the wide traversal) with tmin 0: inside the origin triangle's box and, along their axis,
+    through the box of each of its 21 triangles."""
+    r = np.zeros(3, capi.RAY_DTYPE)
+    for a in range(3):
+        d = np.full(3, 2.0 ** -30)
+        d[a] = 1.0
+        r["d"][a] = (d / np.linalg.norm(d)).astype(np.float32)
+    r["o"] = np.array([2.0 ** -23, 2.0 ** -24, 2.0 ** -25], np.float32)   # every half-extent is at least 2^-22
+    r["tmin"], r["tmax"] = np.float32(0.0), np.float32(np.inf)
+    return r
+
+
+# The inputs on which the LBVH builder's tree is pinned (test_lbvh_host.py, test_gpu_lbvh.py), the
+# smallest that reach each mechanism; triangle counts include the soups' light quad
+LBVH_INPUTS = {
+    **{f"soup{n}": (lambda n=n: soup_total(n)) for n in (1, 2, 3, 255, 256, 257, 20000)},   # 256: the kernels' block
+    "cornell": lambda: cornell((24, 24)),          # several meshes: gid is a global id
+    "sheet": sheet_scene,                          # ext == 0 on z: the quantiser's other branch
+    "identical": identical_scene,                  # one code: index splits, axis 0 throughout
+    "duplicates": duplicates_soup,                 # a run of equal codes inside distinct ones
+    "shifted": shifted_soup,                       # negative, large, cancelling coordinates
+    "signed_zeros": signed_zero_pair,              # bounds -0.0 and +0.0 on one axis
+    "chain65": lambda: chain_scene(65),            # depth 64, the deepest accepted
+}
+
+
+def subtree_leaves(nodes):
+    """For a BVH2 export of one-triangle leaves: (internal records, parents first; sets) where
+    sets[r] = [leaf positions below child 0 of record r, those below child 1], gathered by brute
+    force over the child links."""
+    sets = {}
+    order, todo = [], [int(nodes["child"][0][0])]
+    while todo:
+        r = todo.pop()
+        if r & 0x80000000:
+            continue
+        order.append(r)
+        todo += [int(nodes["child"][r][0]), int(nodes["child"][r][1])]
+    leaf = lambda ref: np.array([(ref & 0x7FFFFFFF) >> 3], np.int64)
+    for r in reversed(order):                      # children before parents
+        kids = [int(nodes["child"][r][k]) for k in (0, 1)]
+        sets[r] = [leaf(c) if c & 0x80000000 else np.concatenate(sets[c]) for c in kids]
+    return order, sets
+
+
+def check_split_planes(nodes, tris, cells):
+    """The split planes of a Morton-code BVH2 export against cells [n_tris, 3] quantised in high
+    precision (lbvh_restate.code_cells_f64), which may differ from the builder's f32 cells by one.
+    Along its `axis` a node's leaves fill part of an aligned block of 2^(k+1) cells, the left subtree
+    in its lower half and the right subtree in its upper half; the plane between the halves is at cell
+    P = (hi >> k) << k, k the highest bit in which the block's lowest and highest occupied cells lo, hi
+    differ.  The high-precision lo and hi are each within one cell of the builder's, so the builder's
+    plane is among the at most nine planes of (lo + {-1, 0, 1}, hi + {-1, 0, 1}); against one of them
+    every left centre must lie below the plane plus one cell (cell <= P) and every right centre above
+    it minus one cell (cell >= P - 1).  Returns the records of the nodes for which none does."""
+    order, sets = subtree_leaves(nodes)
+    gid = tris["gid"].astype(np.int64)
+    cells = np.asarray(cells, np.int64)
+    bad = []
+    for r in order:
+        a = int(nodes["axis"][r])
+        if a > 2:
+            bad.append(r)
+            continue
+        left, right = cells[gid[sets[r][0]], a], cells[gid[sets[r][1]], a]
+        lmax, rmin = int(left.max()), int(right.min())
+        lo, hi = min(int(left.min()), rmin), max(lmax, int(right.max()))
+        ok = False
+        for l in (lo - 1, lo, lo + 1):
+            for h in (hi - 1, hi, hi + 1):
+                if 0 <= l < h <= CHAIN_CELLS:
+                    k = (l ^ h).bit_length() - 1
+                    p = (h >> k) << k
+                    ok = ok or (lmax <= p and rmin >= p - 1)
+        if not ok:
+            bad.append(r)
+    return bad
+
+
 def check_sbvh(cs, nodes, tris, max_leaf, budget=0.5, samples=6):
     """Invariants of an SBVH export (references may be clipped and duplicated): every triangle in
     at least one leaf and at most budget * n extra records, records equal to the mesh, child boxes
