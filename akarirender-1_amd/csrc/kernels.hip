@@ -660,8 +660,10 @@ __global__ __launch_bounds__(kTraceBlock) AKR_TRACE_ATTR void k_trace(TraceArgs 
                 }
                 if (STEPS) steps += busy ? 1 : 0;
                 // lean visits pop at one site with the leaf postponement below (as path_traverse);
-                // the pilot (STEPS) keeps its step metric's old loop, on which the form rule is calibrated
-                constexpr bool kOnePop = TIGHT && !STEPS;
+                // the pilot (STEPS) keeps its step metric's old loop, on which the form rule is calibrated.
+                // Wide kernel only: tmaxp is formed only there; the BVH2 kernel (option wide 0) pops inside
+                // visit_node and culls its any-hit pops at tmax itself
+                constexpr bool kOnePop = WIDE && TIGHT && !STEPS;
                 bool need_pop = false;
                 if (WIDE && busy && is_internal(cur)) {
                     int nt;
@@ -695,7 +697,11 @@ __global__ __launch_bounds__(kTraceBlock) AKR_TRACE_ATTR void k_trace(TraceArgs 
                 }
                 if (busy && !need_pop && leaf == AKR_CHILD_EMPTY && is_leaf(cur)) {
                     leaf = cur;  // postpone the leaf and keep descending
-                    need_pop = true;
+                    // (the BVH2 kernel waits instead: a leaf it reached against the stale best has no box
+                    // of its own to re-test in the leaf phase, so its pop is owed until this leaf's
+                    // triangles have set the best, the reference's order of events)
+                    if (WIDE) need_pop = true;
+                    else cur = AKR_CHILD_POP;
                 }
                 // (an any-hit ray culls at the float below tmax, as the visit's own pop did: an entry at
                 // tmax holds no hit below it)
@@ -762,6 +768,7 @@ __global__ __launch_bounds__(kTraceBlock) AKR_TRACE_ATTR void k_trace(TraceArgs 
                     }
                 }
                 leaf = AKR_CHILD_EMPTY;
+                if (!WIDE && cur == AKR_CHILD_POP) cur = stack_pop(s_stack, stack_ovf, a.ovf_threads, tid, gtid, sp, ANY ? tmax : best);
             }
             if (busy && ((ANY && occluded) || cur == AKR_CHILD_EMPTY)) {
                 busy = false;

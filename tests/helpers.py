@@ -42,6 +42,152 @@ def small_soup(n_tris=20000, resolution=(96, 54), seed=42, r=0.01):
     return scene.soup_scene(n_tris=n_tris, resolution=resolution, seed=seed, r=r)
 
 
+def scaled_soup(k, resolution=(24, 24)):
+    """The 20,000-triangle soup of large triangles (r = 0.2) with every vertex multiplied by 2^k:
+    an exact scaling, so the tree and every hit are the k = 0 scene's, scaled."""
+    sc = small_soup(20_000, resolution, r=0.2)
+    m = sc.shapes[0]
+    m.vertices = (np.asarray(m.vertices, np.float32) * np.float32(2.0 ** k)).astype(np.float32)
+    return sc
+
+
+def scaled_rays(rays, k):
+    """A batch for scaled_soup(k): origins and tmin times 2^k (exact), directions untouched."""
+    r = rays.copy()
+    r["o"] = (r["o"] * np.float32(2.0 ** k)).astype(np.float32)
+    r["tmin"] = (r["tmin"] * np.float32(2.0 ** k)).astype(np.float32)
+    return r
+
+
+def far_origin_rays(k, log2_dist, n=1 << 12, seed=3):
+    """Rays aimed at points of scaled_soup(k) (the origins of random_rays(n, seed, -1, 1), scaled)
+    from the distance 2^log2_dist along their own directions, tmin 0."""
+    r = random_rays(n, seed, -1.0, 1.0, tmin=0.0)
+    target = r["o"].astype(np.float64) * 2.0 ** k
+    r["o"] = (target - r["d"].astype(np.float64) * 2.0 ** log2_dist).astype(np.float32)
+    return r
+
+
+def near_axis_rays(e, n=1 << 12, seed=5):
+    """random_rays(n, seed, -1.2, 1.2) with one direction component per ray, cycling through the
+    axes, overwritten by +-2^e (the sign alternates every three rays)."""
+    r = random_rays(n, seed, -1.2, 1.2)
+    i = np.arange(n)
+    d = r["d"].copy()
+    d[i, i % 3] = np.where((i // 3) % 2 == 0, 1.0, -1.0).astype(np.float32) * np.float32(2.0 ** e)
+    r["d"] = d
+    return r
+
+
+LEAN_REFUSALS = ("tmin", "zero_d", "far_o", "steep", "tmax")
+
+
+def refuse_lean(rays, which, reason):
+    """The rays `which` (a boolean mask) changed so that the lean traversal must refuse them
+    (kernels.hip lean_ok), for one of its reasons: a negative tmin, a zero direction component, an
+    origin component above 2^60, a 1 / d above 2^64, tmax = -inf."""
+    r = rays.copy()
+    idx = np.flatnonzero(which)
+    if reason == "tmin":
+        r["tmin"][idx] = np.float32(-1e-3)
+    elif reason == "zero_d":
+        d = r["d"].copy()
+        d[idx, idx % 3] = np.where(idx % 2 == 0, 0.0, -0.0).astype(np.float32)
+        r["d"] = d
+    elif reason == "far_o":    # aimed at its old origin from 2^61 away
+        r["o"][idx] = (r["o"][idx].astype(np.float64) - r["d"][idx].astype(np.float64) * 2.0 ** 61).astype(np.float32)
+        r["tmin"][idx] = np.float32(0.0)
+    elif reason == "steep":
+        d = r["d"].copy()
+        d[idx, idx % 3] = np.float32(2.0 ** -65)
+        r["d"] = d
+    elif reason == "tmax":
+        r["tmax"][idx] = np.float32(-np.inf)
+    else:
+        raise ValueError(reason)
+    return r
+
+
+def refusal_mask(n, pattern):
+    """Which rays of a batch of n the mixed-wave tests refuse: one lane of each wave of 64, every
+    other lane, all lanes but one, or the second half of each wave."""
+    lane = np.arange(n) % 64
+    return {"1in64": lane == 37, "alternate": lane % 2 == 1, "63in64": lane != 37, "half": lane >= 32}[pattern]
+
+
+def lean_expected(rays, gate=True):
+    """kernels.hip lean_ok restated on a host batch: which rays the tight wide kernel takes through
+    the lean loop (`gate`: the wide view passed the 2^40 test and option lean is on)."""
+    f = np.float32
+    o, d = rays["o"], rays["d"]
+    with np.errstate(divide="ignore", over="ignore"):
+        invd = (f(1.0) / d).astype(f)
+    ok = np.isfinite(o).all(1) & np.isfinite(invd).all(1) & (invd != 0).all(1)
+    ok &= ~np.isnan(rays["tmin"]) & ~np.isnan(rays["tmax"])
+    ok &= (rays["tmin"] >= 0) & (rays["tmax"] > -np.inf)
+    ok &= (np.abs(o).max(1) <= f(2.0 ** 60)) & (np.abs(invd).max(1) <= f(2.0 ** 64))
+    return ok & bool(gate)
+
+
+RAY_STEPS_EXACT = 0xFFFFFFFF    # option ray_steps: the ray went through the exact BVH2 walk
+
+
+def interval_variants(rays, t_hit):
+    """{name: batch}: `rays` (all of which hit at t_hit in the oracle's closest-hit trace) with the
+    interval's ends put on the hit, one float to either side of it, and at the zeros and the smallest
+    subnormal and normal numbers."""
+    f = np.float32
+    t = np.asarray(t_hit, f)
+    out = {}
+    for name, v in (("tmax=t", t), ("tmax=t+", np.nextafter(t, f(np.inf))), ("tmax=t-", np.nextafter(t, f(-np.inf))),
+                    ("tmax=+0", f(0.0)), ("tmax=-0", f(-0.0)), ("tmax=2^-149", f(2.0 ** -149)), ("tmax=2^-126", f(2.0 ** -126))):
+        r = rays.copy()
+        r["tmax"] = v
+        out[name] = r
+    for name, v in (("tmin=t", t), ("tmin=t+", np.nextafter(t, f(np.inf))), ("tmin=t-", np.nextafter(t, f(-np.inf))),
+                    ("tmin=-0", f(-0.0))):
+        r = rays.copy()
+        r["tmin"] = v
+        out[name] = r
+    return out
+
+
+def nonfinite_rays(center=(0.0, 0.0, 0.0)):
+    """A small batch outside every arithmetic assumption: an infinite or NaN origin component, a NaN
+    tmax, a NaN tmin, an all-zero direction, a NaN and an infinite direction component, tmax -inf,
+    tmin +inf (rays 0..11, none of which can hit); rays 12..15 are ordinary."""
+    base = random_rays(16, 41, -0.5, 0.5)
+    base["o"] += np.asarray(center, np.float32)
+    o, d = base["o"].copy(), base["d"].copy()
+    o[0, 0], o[1, 1], o[2, 2] = np.inf, -np.inf, np.nan
+    base["tmax"][3] = np.nan
+    base["tmin"][4] = np.nan
+    d[5] = 0.0
+    d[6] = (0.0, -0.0, 0.0)
+    d[7, 0] = np.nan
+    d[8, 1] = np.inf
+    o[9], d[9] = np.inf, 0.0
+    base["tmax"][10] = -np.inf
+    base["tmin"][11] = np.inf
+    base["o"], base["d"] = o, d
+    return base
+
+
+FAR_CAMERA_SCALE = 30
+FAR_CAMERA_LOG2_Z = 61
+
+
+def far_camera_soup(resolution=(24, 24)):
+    """scaled_soup(30) seen from (0, 0, 2^61) through a field of view that just frames it: every
+    camera ray starts beyond the lean traversal's 2^60 origin bound, every bounce and shadow ray
+    inside it."""
+    sc = scaled_soup(FAR_CAMERA_SCALE, resolution)
+    fov = np.degrees(2.0 * np.arctan(1.6 * 2.0 ** FAR_CAMERA_SCALE / 2.0 ** FAR_CAMERA_LOG2_Z))
+    sc.camera = scene.PerspectiveCamera(position=(0.0, 0.0, 2.0 ** FAR_CAMERA_LOG2_Z), rotation=(0.0, 0.0, 0.0),
+                                        fov=float(fov), resolution=tuple(resolution))
+    return sc
+
+
 def tri_scene(tris, mats, mat_ids, cam):
     """One mesh of unshared-vertex triangles [n, 3, 3] with their geometric normals (up where a
     triangle has no area)."""

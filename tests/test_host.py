@@ -537,23 +537,42 @@ def _f32_fma(a, b, c):
     return (np.float64(a) * np.float64(b) + np.float64(c)).astype(np.float32)
 
 
-def _lean_slot_test(node, slot, o, invd, tmin, lim):
-    """kernels.hip visit_wide_lean for one slot, emulated in f32 (vectorised over rays)."""
+def _f32_fma_exact(a, b, c):
+    """f32 fma at any magnitude: the product of two f32 is exact in f64, the sum is rounded to odd in
+    f64 (TwoSum gives its error exactly), and a round-to-odd value of 53 bits rounds to 24 bits or
+    fewer (a subnormal result) as the exact sum does."""
+    p = np.asarray(a, np.float64) * np.asarray(b, np.float64)
+    c = np.asarray(c, np.float64)
+    p, c = np.broadcast_arrays(p, c)
+    with np.errstate(all="ignore"):   # an infinite operand or sum: err is NaN and s stands
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        even = (s.view(np.int64) & 1) == 0
+        odd = np.nextafter(s, np.where(err > 0, np.inf, -np.inf))
+        return np.where((err != 0) & even, odd, s).astype(np.float32)
+
+
+def _lean_slot_test(node, slot, o, invd, tmin, lim, fma=_f32_fma, parts=None):
+    """kernels.hip visit_wide_lean for one slot, emulated in f32 (vectorised over rays).  `parts`, a
+    list, receives every intermediate array."""
     f = np.float32
     meta = int(node["meta"])
     s = np.array([np.float32(2.0 ** (((meta >> (8 * a)) & 0xFF) - 127)) for a in range(3)], np.float32)
     sc = (s[None, :] * invd).astype(f)
     oq = ((node["origin"][None, :].astype(f) - o).astype(f) * invd).astype(f)
-    e = _f32_fma(_f32_fma(f(255.0), np.abs(sc), np.abs(oq)), f(2.0 ** -21), f(2.0 ** -120))
+    e = fma(fma(f(255.0), np.abs(sc), np.abs(oq)), f(2.0 ** -21), f(2.0 ** -120))
     no, fo = (oq - e).astype(f), (oq + e).astype(f)
     q = [[(int(node["q"][2 * a + hi]) >> (8 * slot)) & 0xFF for hi in (0, 1)] for a in range(3)]
     pos = invd > 0
     qn = np.stack([np.where(pos[:, a], q[a][0], q[a][1]) for a in range(3)], 1).astype(f)
     qf = np.stack([np.where(pos[:, a], q[a][1], q[a][0]) for a in range(3)], 1).astype(f)
-    n = _f32_fma(qn, sc, no)
-    x = _f32_fma(qf, sc, fo)
+    n = fma(qn, sc, no)
+    x = fma(qf, sc, fo)
     t = np.maximum(n.max(1), tmin)
     m1 = np.minimum(x.min(1), lim)
+    if parts is not None:
+        parts += [sc, oq, e, no, fo, n, x]
     return t <= m1, t
 
 
@@ -652,6 +671,218 @@ def test_lean_slot_test_conservative_on_grid_bounds():
         checked += int(rh.sum())
     assert checked > 30_000
     assert bad == 0
+
+
+def test_f32_fma_exact_matches_libm():
+    """The exact f32 fma of the stated-bounds test against libm's fmaf, on operands spread over the
+    whole exponent range (where the f64 emulation _f32_fma double-rounds) and on halfway cases."""
+    import ctypes.util
+    libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    libm.fmaf.restype = C.c_float
+    libm.fmaf.argtypes = [C.c_float] * 3
+    rng = np.random.default_rng(17)
+    f = np.float32
+    n = 20_000
+    mant = lambda: (1.0 + rng.integers(0, 1 << 23, n) / float(1 << 23)) * rng.choice([-1.0, 1.0], n)
+    a = (mant() * 2.0 ** rng.integers(-60, 60, n)).astype(f)
+    b = (mant() * 2.0 ** rng.integers(-60, 60, n)).astype(f)
+    ab = a.astype(np.float64) * b.astype(np.float64)
+    # addends from far below the product to far above it, and within a few binades (cancellation)
+    c = (-ab * 2.0 ** rng.choice([-60, -30, -25, -24, -23, -1, 0, 1, 23, 24, 25, 40], n) * rng.choice([1.0, -1.0, 1.0 + 2.0 ** -20], n))
+    with np.errstate(over="ignore", under="ignore"):
+        c = c.astype(f)
+    a[:256], b[:256] = f(255.0), (mant()[:256] * 2.0 ** rng.integers(-149, -120, 256)).astype(f)   # subnormal products
+    c[:256] = (mant()[:256] * 2.0 ** rng.integers(-149, -120, 256)).astype(f)
+    # (1 + 2^-12)^2 = 1 + 2^-11 + 2^-24 lies halfway between two f32; an addend of 2^-80 decides the side
+    k = 2.0 ** rng.integers(-30, 30, 256)
+    a[256:512], b[256:512] = ((1 + 2.0 ** -12) * k).astype(f), f(1 + 2.0 ** -12)
+    c[256:512] = (rng.choice([-1.0, 1.0], 256) * 2.0 ** -80 * k).astype(f)
+    want = np.array([libm.fmaf(float(x), float(y), float(z)) for x, y, z in zip(a, b, c)], f)
+    got = _f32_fma_exact(a, b, c)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.count_nonzero(_f32_fma(a, b, c) != want) > 0   # the f64 emulation is not exact out here
+
+
+def _grid_box(rng, org, e):
+    """A wide-node frame (origin `org`, steps 2^e) and the tightest f32 box inside one of its grid
+    cells' hull [org + q_lo 2^e, org + q_hi 2^e]: the builder's zero-slack case (it quantizes outward
+    in real arithmetic).  Returns (node, lo, hi), or None where no f32 lies inside on some axis."""
+    from fractions import Fraction
+    f = np.float32
+    q_lo = rng.integers(0, 128, 3)
+    q_hi = q_lo + rng.integers(0, 128, 3)
+
+    def inside(x, up):   # the f32 nearest to x that is >= x (up) or <= x
+        v = f(float(x))
+        while up and Fraction(float(v)) < x:
+            v = np.nextafter(v, f(np.inf))
+        while not up and Fraction(float(v)) > x:
+            v = np.nextafter(v, f(-np.inf))
+        return v
+    lo = np.array([inside(Fraction(float(org[a])) + int(q_lo[a]) * Fraction(2) ** int(e[a]), True) for a in range(3)], f)
+    hi = np.array([inside(Fraction(float(org[a])) + int(q_hi[a]) * Fraction(2) ** int(e[a]), False) for a in range(3)], f)
+    if np.any(lo > hi):
+        return None
+    node = np.zeros((), [("origin", f, 3), ("meta", np.uint32), ("q", np.uint32, 6)])
+    node["origin"] = org
+    node["meta"] = int(e[0] + 127) | int(e[1] + 127) << 8 | int(e[2] + 127) << 16
+    node["q"] = [int(q_lo[0]), int(q_hi[0]), int(q_lo[1]), int(q_hi[1]), int(q_lo[2]), int(q_hi[2])]
+    return node, lo, hi
+
+
+def _stated_bounds_rays(rng, m, lo, hi, ld_choices, off_exp):
+    """m rays aimed at corner / edge / face / inner points of the box: direction components
+    +-mantissa * 2^ld, ld drawn per ray from one of `ld_choices` (a (low, high) range shared by the
+    axes), the origin so far back that the largest |d| T is about 2^off_exp.  f32 (o, d, T)."""
+    f = np.float32
+    sel = rng.integers(0, 4, (m, 3))
+    mid = (lo.astype(np.float64) + hi.astype(np.float64)) / 2
+    inner = lo.astype(np.float64) + (hi.astype(np.float64) - lo.astype(np.float64)) * rng.random((m, 3))
+    tgt = np.where(sel == 0, lo, np.where(sel == 1, hi, np.where(sel == 2, mid, inner)))
+    rg = np.array(ld_choices)[rng.integers(0, len(ld_choices), m)]
+    ld = rng.integers(rg[:, :1], rg[:, 1:] + 1, (m, 3))
+    mant = np.where(rng.random((m, 3)) < 0.3, 1.0, 1.0 + rng.integers(0, 1 << 23, (m, 3)) / float(1 << 23))
+    d = (rng.choice([-1.0, 1.0], (m, 3)) * mant * 2.0 ** ld).astype(f)
+    T = 2.0 ** (rng.integers(off_exp[0], off_exp[1] + 1, m) - ld.max(1)) * rng.uniform(0.25, 1.0, m)
+    with np.errstate(over="ignore", under="ignore"):
+        o = (tgt - d.astype(np.float64) * T[:, None]).astype(f)
+        T = T.astype(f)
+    return o, d, T
+
+
+# (name, log2 of the frame origin's magnitude (None: the origin is a small multiple of the step), step
+#  exponents, per-ray ranges of log2 |d|, log2 of the distance |d| T from the box to the origin)
+_STATED_BOUNDS_REGIMES = [
+    # frames at the 2^40 gate, origins out to 2^60, all three 1 / d at 2^64: oq and the slot values near 2^124
+    ("top", (36, 40), (24, 40), [(-64, -64), (-64, -62), (-64, -40), (-30, 0)], (52, 60)),
+    # every scale up to the gate, unit-length-like directions with components down to 2^-64
+    ("middle", (-8, 40), None, [(-64, 0), (-12, 0), (-2, 0)], None),
+    # steps at the bottom of the exponent range: sc = 2^e / d underflows for |d| > 1
+    ("bottom", None, (-126, -112), [(0, 20), (-10, 10), (-64, 0), (0, 0)], None),
+]
+
+
+def test_lean_slot_test_conservative_at_stated_bounds():
+    """The lean slot test's claim (kernels.hip, above visit_wide_lean_node) at the bounds it states:
+    frame origins and steps up to 2^40, ray origins up to 2^60, |1 / d| up to 2^64, and steps down to
+    2^-126 where sc underflows and the 2^-120 term is the slack.  Every fma is exact (_f32_fma_exact).
+    For every ray that lean_ok admits: no intermediate is NaN or infinite; where the reference test of
+    the exact box accepts, the lean test accepts, with an entry distance no larger."""
+    rng = np.random.default_rng(23)
+    f = np.float32
+    m = 96
+    checked, admitted = {}, 0
+    for name, org_exp, e_rng, ld_choices, off_exp in _STATED_BOUNDS_REGIMES:
+        checked[name] = 0
+        for b in range(1500):
+            if name == "top":
+                e = rng.integers(e_rng[0], e_rng[1] + 1, 3)
+                org = np.clip(rng.uniform(-1, 1, 3) * 2.0 ** rng.integers(org_exp[0], org_exp[1] + 1, 3), -2.0 ** 40, 2.0 ** 40).astype(f)
+                if b % 8 == 0:
+                    org[rng.integers(0, 3)] = f(rng.choice([-1.0, 1.0]) * 2.0 ** 40)
+                off = off_exp
+            elif name == "middle":
+                k = int(rng.integers(org_exp[0], org_exp[1] + 1))
+                org = (rng.uniform(-1, 1, 3) * 2.0 ** k).astype(f)
+                e = np.minimum(rng.integers(-20, 12, 3) + k, 40)
+                top_e = int(e.max()) + 7       # the box is at most 2^(e + 8) wide
+                off = (top_e - 8, min(60, top_e + 14))
+            else:
+                e = rng.integers(e_rng[0], e_rng[1] + 1, 3)
+                org = (rng.integers(-1024, 1025, 3) * 2.0 ** e.min()).astype(f)
+                off = (int(e.min()), int(e.max()) + 10)
+            box = _grid_box(rng, org, e)
+            if box is None:
+                continue
+            node, lo, hi = box
+            o, d, T = _stated_bounds_rays(rng, m, lo, hi, ld_choices, off)
+            with np.errstate(all="ignore"):
+                invd = (f(1.0) / d).astype(f)
+                ok = (np.isfinite(o).all(1) & np.isfinite(invd).all(1) & (invd != 0).all(1)
+                      & (np.abs(o).max(1) <= f(2.0 ** 60)) & (np.abs(invd).max(1) <= f(2.0 ** 64)))   # lean_ok
+                o, invd, T = o[ok], invd[ok], T[ok]
+                n = len(o)
+                admitted += n
+                for tmin, tmax in ((np.zeros(n, f), np.full(n, np.inf, f)), ((T * f(0.5)).astype(f), (T * f(2.0)).astype(f))):
+                    fin = np.isfinite(tmax)
+                    tmaxp = np.where(fin, np.nextafter(tmax, f(-np.inf)), np.finfo(f).max).astype(f)   # float_below; fminf(best, +inf)
+                    rh, rt = _ref_box_test(lo, hi, o, invd, tmin, tmax, np.full(n, np.inf, f))
+                    parts = []
+                    lh, lt = _lean_slot_test(node, 0, o, invd, tmin, tmaxp, fma=_f32_fma_exact, parts=parts)
+                    for p in parts:
+                        assert np.isfinite(p).all(), f"{name}: a NaN or infinite intermediate (box {b})"
+                    assert np.all(lh[rh]), f"{name}: the lean test rejects a box the reference enters (box {b})"
+                    assert np.all(lt[rh] <= rt[rh]), f"{name}: a lean entry distance above the reference's (box {b})"
+                    checked[name] += int(rh.sum())
+    print(f"lean slot test at its stated bounds: accepted cases checked {checked}, of {admitted} admitted rays")
+    assert sum(checked.values()) >= 30_000
+    assert min(checked.values()) >= 3_000, checked   # no regime passes on rejections alone
+
+
+def test_traversal_limit_inputs_on_the_oracle():
+    """The conditions test_gpu_trace_limits.py relies on, on the oracle alone (a host-built tree): the
+    hit shares of the scaled, far-origin and near-axis batches, on which side of the 2^40 gate each
+    scaled wide view lies, which rays lean_ok admits, that every interval variant changes oracle
+    answers across its edge, and the share of the far camera's pixels whose paths go on."""
+    import helpers as H
+    share = lambda h: float((h["gid"] != 0xFFFFFFFF).mean())
+    base = random_rays(1 << 14, 2, -1.2, 1.2)
+    orcs = {}
+    for k in (0, 20, 38, 39, 40):
+        cs = scene.compile_scene(H.scaled_soup(k))
+        nodes, tris, _, (wn, _, _) = capi.build_bvh_host(cs.vertices, cs.indices, wide=True)
+        orcs[k] = orc = O.OracleScene(cs, nodes, tris, capi)
+        steps = 2.0 ** (np.stack([(wn["meta"] >> (8 * a)) & 0xFF for a in range(3)]).astype(np.int64).max() - 127)
+        max_abs = max(float(np.abs(wn["origin"]).max()), steps)
+        assert (max_abs <= 2.0 ** 40) == (k <= 39), (k, max_abs)
+        rays = H.scaled_rays(base, k)
+        assert H.lean_expected(rays).all()
+        for any_hit in (False, True):
+            s = share(orc.trace(rays, any_hit=any_hit)[0])
+            assert abs(s - 0.8256) < 1e-4, (k, any_hit, s)     # pure scaling: the same share at every k
+    for k, want in ((0, (0.61, 0.61)), (38, (0.78, 0.24))):
+        for log2_dist, w in zip((59, 61), want):
+            rays = H.far_origin_rays(k, log2_dist)
+            assert np.all(H.lean_expected(rays) == (log2_dist == 59))
+            s = share(orcs[k].trace(rays)[0])
+            assert abs(s - w) < 0.01 and s >= 0.2, (k, log2_dist, s)
+    for e in (-62, -63, -64, -65, -66):
+        rays = H.near_axis_rays(e)
+        assert np.all(H.lean_expected(rays) == (e >= -64))
+        s = share(orcs[0].trace(rays)[0])
+        assert abs(s - 0.8213) < 1e-4, (e, s)
+    n = 4096 + 17
+    for reason in H.LEAN_REFUSALS:
+        for pattern in ("1in64", "alternate", "63in64", "half"):
+            mask = H.refusal_mask(n, pattern)
+            assert np.array_equal(H.lean_expected(H.refuse_lean(random_rays(n, 7, -1.2, 1.2), mask, reason)), ~mask)
+    # intervals that end on a hit
+    crays = random_rays(1 << 12, 6, -0.9, 0.9)
+    crays["o"][:, 1] += 1.0
+    ccs = scene.compile_scene(cornell((24, 24)))
+    corc = O.OracleScene(ccs, *capi.build_bvh_host(ccs.vertices, ccs.indices)[:2], capi)
+    for orc, rays in ((orcs[0], random_rays(1 << 12, 6, -1.2, 1.2)), (corc, crays)):
+        for exact in (False, True):
+            oh = orc.trace(rays, exact_cull=exact)[0]
+            hit = oh["gid"] != 0xFFFFFFFF
+            assert hit.mean() >= 0.5
+            variants = H.interval_variants(rays[hit], oh["t"][hit])
+            for any_hit in (False, True):
+                ans = {v: orc.trace(r, any_hit=any_hit, exact_cull=exact)[0] for v, r in variants.items()}
+                ans[None] = orc.trace(rays[hit], any_hit=any_hit, exact_cull=exact)[0]
+                for v in variants:
+                    other = ans[{"tmax=t+": "tmax=t", "tmin=t-": "tmin=t"}.get(v)]
+                    assert np.any((ans[v]["gid"] != other["gid"]) | (ans[v]["t"] != other["t"])), (v, any_hit, exact)
+        nf = orc.trace(H.nonfinite_rays((0.0, 1.0, 0.0) if orc is corc else (0.0, 0.0, 0.0)))[0]
+        assert (nf["gid"][12:] != 0xFFFFFFFF).all() and (nf["gid"][:12] == 0xFFFFFFFF).all()
+    # the far camera: a finite film, and most paths go on past the camera ray
+    cs = scene.compile_scene(H.far_camera_soup((24, 24)))
+    orc = O.OracleScene(cs, *capi.build_bvh_host(cs.vertices, cs.indices)[:2], capi)
+    rad, w, _, probe = orc.render(4, 5, probe=True)
+    going = float((probe["closest_rays"] > 4).mean())
+    print(f"far camera: {going:.4f} of the pixels trace more than spp closest rays, mean {probe['closest_rays'].mean():.1f} "
+          f"closest and {probe['shadow_rays'].mean():.1f} shadow rays")
+    assert np.isfinite(rad).all() and rad.mean() > 0 and going >= 0.4
 
 
 def test_device_trig_matches_libm_on_path_range(tmp_path):
