@@ -145,6 +145,7 @@ COLLAPSE_SAH, COLLAPSE_BALANCED = 0, 1   # akr_build_params::wide_collapse
 MAT_DIFFUSE, MAT_GLOSSY, MAT_EMISSIVE, MAT_MIX = 0, 1, 2, 3
 PROBE_SEED, PROBE_RAYS = 1, 2
 FORM_NAMES = {-1: None, 0: "wavefront", 2: "k_path", 3: "k_path_defer", 4: "k_path_spec"}
+SHADING_NAMES = {-1: None, 0: "general", 1: "simple"}   # AKR_SHADING_* (akr_hip_render_shading)
 
 # numpy views of the POD structs (for vectorised ray/hit buffers)
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmin", np.float32), ("d", np.float32, 3), ("tmax", np.float32)])
@@ -202,6 +203,7 @@ EXPORTS = {
     "akr_hip_render_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "akr_hip_synchronize": (C.c_int, [_P]),
     "akr_hip_render_form": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "akr_hip_render_shading": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "akr_hip_render_form_inputs": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "akr_hip_pixel_probe": (C.c_int, [_P, _P, C.c_uint64]),
     "akr_bvh_host_build": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(BuildParams), C.POINTER(_P),
@@ -810,10 +812,14 @@ class HipContext:
                                            max_ms=arr[i].max_ms) for i in range(n.value)}
 
     def render_info(self) -> dict:
-        """Lanes per pixel (always 1) and sample passes of the last render (1 for a persistent form)."""
-        lanes, passes = C.c_int32(0), C.c_int32(0)
+        """Lanes per pixel (always 1) and sample passes of the last render (1 for a persistent form), and
+        the shading build it ran (SHADING_NAMES)."""
+        lanes, passes, shading = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         self._check(self.lib.akr_hip_render_info(self.h, C.byref(lanes), C.byref(passes)))
-        return {"lanes": lanes.value, "passes": passes.value}
+        if hasattr(self.lib, "akr_hip_render_shading"):   # an experiment build may predate the export
+            self._check(self.lib.akr_hip_render_shading(self.h, C.byref(shading)))
+        return {"lanes": lanes.value, "passes": passes.value,
+                "shading": SHADING_NAMES.get(shading.value, str(shading.value))}
 
     def render_form(self) -> dict:
         """The form that ran the last path render (FORM_NAMES) and whether its pixel fetch was

@@ -25,6 +25,7 @@
 #include "options.h"
 #include "leaf_layout.h"
 #include "path_plan.h"
+#include "shade_simple.h"
 
 using namespace akr;
 
@@ -210,6 +211,11 @@ struct akr_hip_ctx {
     int32_t n_mats = 0;
     bool has_image_tex = false;
     bool simple_shading = true;  // every material Diffuse / Emissive with constant textures
+    // the committed tables allow the persistent kernels' simple shading build (shade_simple.h); set by every
+    // commit_scene(), so it follows the scene a render sees.  simple_shading above chooses the form, this
+    // the build: an image texture no material uses keeps the wavefront form but not the general build
+    bool shade_simple = false;
+    int32_t last_shading = AKR_SHADING_NONE;  // akr_hip_render_shading
 
     CameraDev cam{};
     bool cam_set = false;
@@ -368,7 +374,9 @@ struct akr_hip_ctx {
     DBuf<uint32_t> d_work;  // dynamic-fetch counters of a standalone trace launch (kTraceWords)
     uint32_t ovf_threads = 0;
     uint32_t trace_grid[3] = {0, 0, 0};
-    uint32_t path_grid[3][2] = {{0, 0}, {0, 0}, {0, 0}};  // resident workgroups of the persistent path kernels [kind][tab]
+    // resident workgroups of the persistent path kernels' product builds [kind][tab][leaf_one][simple]: of the
+    // kernel launch_path() launches for them
+    uint32_t path_grid[3][2][2][2] = {};
     // the render form rule is plan_path() in path_plan.h; its knobs are in `opt`
     // the last render's form inputs (akr_hip_render_form_inputs): pixels per lane x 1000, the pilot's
     // rays and their summed steps
@@ -541,21 +549,7 @@ struct akr_hip_ctx {
             const akr_material &x = mats[m];
             MatDev &d = md[m];
             std::memset(&d, 0, sizeof(d));
-            d.type = x.type;
-            d.double_sided = x.double_sided;
-            d.first = x.first;
-            d.second = x.second;
-            d.color_img = d.rough_img = d.frac_img = -1;
-            auto resolve = [&](int32_t ti, float *val, int n, int32_t &img) {
-                if (ti < 0 || ti >= (int32_t)texs.size()) return;  // unused by this material type
-                if (texs[ti].type == AKR_TEX_IMAGE) img = ti;
-                else
-                    for (int c = 0; c < n; c++) val[c] = texs[ti].value[c];
-            };
-            if (x.type == AKR_MAT_DIFFUSE || x.type == AKR_MAT_EMISSIVE || x.type == AKR_MAT_GLOSSY)
-                resolve(x.color, d.color, 3, d.color_img);
-            if (x.type == AKR_MAT_GLOSSY) resolve(x.roughness, &d.rough, 1, d.rough_img);
-            if (x.type == AKR_MAT_MIX) resolve(x.fraction, &d.frac, 1, d.frac_img);
+            akr::resolve_material(x, texs.data(), texs.size(), d);  // shade_simple.h
         }
         d_mats.upload(md.data(), md.size(), stream);
         n_mats = (int32_t)md.size();
@@ -593,9 +587,7 @@ struct akr_hip_ctx {
                 x.tc[2 * k + 0] = texcoords[6 * g + 2 * k + 0];
                 x.tc[2 * k + 1] = texcoords[6 * g + 2 * k + 1];
             }
-            const akr_texture &lt = texs[mats[m].color];
-            x.color_img = lt.type == AKR_TEX_IMAGE ? mats[m].color : -1;
-            for (int c = 0; c < 3; c++) x.Le[c] = lt.type == AKR_TEX_IMAGE ? 0.0f : lt.value[c];
+            akr::resolve_emission(texs.data(), texs.size(), mats[m].color, x);  // an image: color_img, Le 0
             // AreaLight::sample's triangle constants (light.h:58-71), in the device's f32 order:
             // lx = cross(v1 - v0, v2 - v0) (math.h:176-181), lng = lx / sqrt(dot(lx, lx)),
             // area_half = sqrt(dot(lx, lx)) * 0.5
@@ -624,6 +616,8 @@ struct akr_hip_ctx {
         for (size_t i = 0; i < n; i++) ld[i].sel_pdf = func[i] / (func_int * (float)n_lights);  // scene.h:85-89
         d_lights.upload(ld.data(), ld.size(), stream);
         d_cdf.upload(cdf.data(), cdf.size(), stream);
+        // which shading build these tables allow: decided on the records just uploaded
+        shade_simple = akr::shade_tables_simple(md.data(), md.size(), ld.data(), ld.size());
         // the selection pdf by triangle: what a BSDF-sampled ray that hits a listed triangle
         // weighs NEE's pdf of the same point with; uploaded when a session starts with option "mis"
         tri_sel.assign(matid.size(), 0.0f);
@@ -642,9 +636,10 @@ struct akr_hip_ctx {
             mx = std::max(mx, trace_grid[m]);
         }
         for (int d = 0; d < 3; d++)
-            for (int t = 0; t < 2; t++) {
-                path_grid[d][t] = (uint32_t)(n_cu * path_blocks_per_cu(d, t != 0));
-                mx = std::max(mx, path_grid[d][t]);
+            for (int k = 0; k < 8; k++) {
+                const int t = k >> 2, l = (k >> 1) & 1, s = k & 1;
+                path_grid[d][t][l][s] = (uint32_t)(n_cu * path_blocks_per_cu(d, t != 0, l != 0, s != 0));
+                mx = std::max(mx, path_grid[d][t][l][s]);
             }
         ovf_threads = mx * kTraceBlock;
         d_ovf.reserve((size_t)ovf_threads * (kStackMax - kStackLds));
@@ -830,8 +825,8 @@ struct akr_hip_ctx {
         pp.fault_test = 0;
         pp.state_in = pp.state_out = nullptr;
         const uint32_t grid = (uint32_t)std::max<uint64_t>(
-            1, std::min<uint64_t>(path_grid[PATH_PLAIN][tab], ((uint64_t)N + kTraceBlock - 1) / kTraceBlock));
-        launch_path(true, PATH_PLAIN, tab, leaf_one_kernel, pp, grid, ms);
+            1, std::min<uint64_t>(path_grid[PATH_PLAIN][tab][1][1], ((uint64_t)N + kTraceBlock - 1) / kTraceBlock));
+        launch_path(true, PATH_PLAIN, tab, leaf_one_kernel, false, pp, grid, ms);  // counting: the general shading
         HIPCHK(hipMemsetAsync(d_film.p, 0, (size_t)N * sizeof(float4), ms));
     }
 
@@ -1143,6 +1138,7 @@ struct akr_hip_ctx {
         last_passes = 0;
         last_form = AKR_FORM_NONE;
         last_ordered = 0;
+        last_shading = AKR_SHADING_NONE;
         form_pending = pilot_sum_pending = false;
         probe_ok = false;
         probe_n = 0;
@@ -1243,6 +1239,9 @@ struct akr_hip_ctx {
         pa.pop_rounds = (uint32_t)opt.path_pop_rounds;
         // the shading's material / light / CDF tables in LDS when they fit
         const bool tab = opt.path_tab && path_tab_fits(n_mats, n_lights);
+        // the shading build: the simple one where the committed tables allow it; the
+        // counting builds run the general one on every scene
+        const bool simple = shade_simple && !opt.count;
         PathPlanIn in;
         in.N = N;
         in.M = r.M;
@@ -1252,7 +1251,7 @@ struct akr_hip_ctx {
         in.subset = r.subset != nullptr;
         in.n_tris = n_tris();
         in.bvh_dev_bytes = bvh_dev_bytes;
-        for (int k = 0; k < 3; k++) in.grid[k] = path_grid[k][tab];
+        for (int k = 0; k < 3; k++) in.grid[k] = path_grid[k][tab][leaf_one_kernel][simple];
         in.block = kTraceBlock;
         const PathPlan pl = plan_path(in, opt);
         last_ppl1000 = pl.ppl1000;
@@ -1289,9 +1288,11 @@ struct akr_hip_ctx {
             }
         }
         timed("path", ms, [&] {  // one timed record: a gated launch that exits at once adds microseconds
-            for (int k = 0; k < pl.n_launch; k++) launch_path(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, args[k], pl.launch[k].grid, ms);
+            for (int k = 0; k < pl.n_launch; k++)
+                launch_path(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, simple, args[k], pl.launch[k].grid, ms);
         });
         HIPCHK(hipGetLastError());
+        last_shading = simple ? AKR_SHADING_SIMPLE : AKR_SHADING_GENERAL;
         form_pending = pl.gated;
         pilot_sum_pending = pl.want_steps && !pl.gated;  // the step sum is read back on request
         if (pl.gated) std::copy(pl.gate_forms, pl.gate_forms + 2, gate_forms);
@@ -1314,6 +1315,7 @@ struct akr_hip_ctx {
         hipStream_t ms = main_st;
         const SceneDev sd = scene_dev();
         if (p.spp > 0) last_form = AKR_FORM_WAVEFRONT;
+        if (p.spp > 0) last_shading = AKR_SHADING_GENERAL;
         const int nb = p.max_depth == 0 ? 1 : p.max_depth;  // the trace at depth == max_depth can
                                                              // add nothing: skipped
         int64_t g = 0;  // bounce index over all passes: shadow queues alternate by its parity
@@ -3116,6 +3118,12 @@ int akr_hip_render_form(akr_hip_ctx *ctx, int32_t *form, int32_t *ordered) {
         ctx->resolve_form();
         if (form) *form = ctx->last_form;
         if (ordered) *ordered = ctx->last_ordered;
+    });
+}
+
+int akr_hip_render_shading(akr_hip_ctx *ctx, int32_t *shading) {
+    return guard(ctx, [&] {
+        if (shading) *shading = ctx->last_shading;
     });
 }
 

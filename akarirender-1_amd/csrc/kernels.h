@@ -28,8 +28,11 @@ void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st);
 void launch_ao_resolve(const AoResolveArgs &a, uint32_t max_items, hipStream_t st);
 // persistent path kernel forms: PATH_PLAIN / PATH_DEFER / PATH_SPEC (akr_path_forms.h)
 // leaf_one: PATH_PLAIN's product build with the one-triangle leaf phase (k_path) or without (k_path_general)
-void launch_path(bool count, int kind, bool tab, bool leaf_one, const PathArgs &a, uint32_t grid, hipStream_t st);
-int path_blocks_per_cu(int kind, bool tab);
+// simple: the product builds' shading for tables of constant Diffuse / Emissive (shade_simple.h); the counting
+// builds and simple = false run the general shading
+void launch_path(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathArgs &a, uint32_t grid,
+                 hipStream_t st);
+int path_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple);  // of the product build launch_path would launch
 bool path_tab_fits(int32_t n_mats, int32_t n_lights);
 void launch_check_weights(const float4 *film, uint32_t n, float expect, uint32_t *bad, hipStream_t st);
 void launch_merge_film(const float4 *film, const uint32_t *pixel, const uint32_t *order, uint32_t n, int32_t width,

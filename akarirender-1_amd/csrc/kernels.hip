@@ -1127,7 +1127,17 @@ struct MisOut {
     float4 carry;  // for the extension ray; .w 0: nothing
 };
 
-template <class Tab, bool ENV = false, bool MIS = false>
+// SIMPLE: the build for scenes whose tables hold constant Diffuse / Emissive only (shade_simple.h
+// shade_tables_simple): no texcoord fetch, every channel and every light's emission its record's constant,
+// no Mix selection, the closure Diffuse once the Emissive case has returned.  What remains is the general
+// build's operations in its order.
+template <bool SIMPLE, class C>
+__device__ __forceinline__ V3 chan_rgb(const SceneDev &s, const C &c, int32_t img, V2 tc) {
+    if constexpr (SIMPLE) return v3(c[0], c[1], c[2]);
+    else return mat_rgb(s, c, img, tc);
+}
+
+template <class Tab, bool ENV = false, bool MIS = false, bool SIMPLE = false>
 __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab, uint32_t gid, float u, float v, V3 wo,
                                               V3 beta, uint32_t &seed, int depth, int max_depth, bool last, Bounce &o,
                                               unsigned long long *t_load = nullptr, const EnvDev *env = nullptr,
@@ -1150,7 +1160,7 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
     const V3 ng = normalize(cross(sub(v1, v0), sub(v2, v0)));
     const V3 ns = lerp3(v3(tr.b.w, tr.c.w, tr.d.x), v3(tr.d.y, tr.d.z, tr.d.w), v3(tr.e.x, tr.e.y, tr.e.z), u, v);
     V2 tc{0.0f, 0.0f};  // only image textures read it
-    if (s.has_image_tex) {
+    if (!SIMPLE && s.has_image_tex) {
         const AKR_GLOBAL float *tt = s.texcoords + 6 * (size_t)gid;
         tc = lerp3(V2{tt[0], tt[1]}, V2{tt[2], tt[3]}, V2{tt[4], tt[5]}, u, v);
     }
@@ -1160,7 +1170,7 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
             const bool face_front = dot(neg(wo), ng) < 0.0f;
             if (mat->double_sided || face_front) {
                 o.emit = true;
-                o.e = mul(beta, mat_rgb(s, mat->color, mat->color_img, tc));
+                o.e = mul(beta, chan_rgb<SIMPLE>(s, mat->color, mat->color_img, tc));
             }
         }
         if constexpr (MIS) {
@@ -1192,7 +1202,7 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
     float choice_pdf = 1.0f;
     [[maybe_unused]] bool pair = false;  // MIS: not the last vertex, and not reached through a Mix (whose BSDF draw is the selection's)
     if constexpr (MIS) pair = !last && mat->type != AKR_MAT_MIX;
-    while (mat->type == AKR_MAT_MIX) {  // Material::select_material, material.h:251-268
+    while (!SIMPLE && mat->type == AKR_MAT_MIX) {  // Material::select_material, material.h:251-268
         const float frac = mat_x(s, mat->frac, mat->frac_img, tc);
         if (sel_u < frac) {
             sel_u = sel_u / frac;
@@ -1205,9 +1215,9 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
         }
     }
     Closure cl{CL_NONE, v3(0, 0, 0), 0.0f};
-    if (mat->type == AKR_MAT_DIFFUSE) {
+    if (SIMPLE || mat->type == AKR_MAT_DIFFUSE) {  // SIMPLE: what is not Emissive is Diffuse
         cl.kind = CL_DIFFUSE;
-        cl.R = mat_rgb(s, mat->color, mat->color_img, tc);
+        cl.R = chan_rgb<SIMPLE>(s, mat->color, mat->color_img, tc);
     } else if (mat->type == AKR_MAT_GLOSSY) {
         cl.kind = CL_GLOSSY;
         cl.R = mat_rgb(s, mat->color, mat->color_img, tc);
@@ -1279,7 +1289,7 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
         const float dist_sqr = dot(lwi, lwi);
         lwi = divs(lwi, sqrtf(dist_sqr));
         V3 Le;
-        if (lt.color_img < 0) {
+        if (SIMPLE || lt.color_img < 0) {
             Le = ld3(lt.Le);
         } else {
             const V2 ltc = lerp3(V2{lt.tc[0], lt.tc[1]}, V2{lt.tc[2], lt.tc[3]}, V2{lt.tc[4], lt.tc[5]}, b0, b1);
@@ -1311,6 +1321,14 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
         o.e0 = make_float4(p.x, p.y, p.z, kEps / cng);
         o.e1 = make_float4(wi.x, wi.y, wi.z, kInf);
     }
+}
+
+// the persistent path kernels' call: the table's type deduced, the shading build named
+template <bool SIMPLE, class Tab>
+__device__ __forceinline__ void shade_hit_path(const SceneDev &s, const Tab &tab, uint32_t gid, float u, float v, V3 wo,
+                                               V3 beta, uint32_t &seed, int depth, int max_depth, bool last, Bounce &o,
+                                               unsigned long long *t_load = nullptr) {
+    shade_hit_tab<Tab, false, false, SIMPLE>(s, tab, gid, u, v, wo, beta, seed, depth, max_depth, last, o, t_load);
 }
 
 __device__ __forceinline__ void shade_hit(const SceneDev &s, uint32_t gid, float u, float v, V3 wo, V3 beta,
@@ -2198,7 +2216,8 @@ constexpr int kParkSlots = 8;
 
 // ONE: the product leaf phase is path_leaf_masks (k_path); else path_leaf's general form for every wave
 // (k_path_general, the kernel of scenes whose leaves mostly hold several triangles: leaf_layout.h leaf_one_pays)
-template <bool COUNT, bool TAB, bool ONE>
+// SIMPLE: shade_hit_tab's build for tables of constant Diffuse / Emissive (shade_simple.h)
+template <bool COUNT, bool TAB, bool ONE, bool SIMPLE>
 __device__ __forceinline__ void path_plain(const PathArgs &pa) {
     if (pa.gate && *pa.gate != pa.gate_want) return;  // the other candidate form runs (uniform: before any barrier)
     const TraceArgs &a = pa.t;
@@ -2307,8 +2326,8 @@ __device__ __forceinline__ void path_plain(const PathArgs &pa) {
                         mark_lines(pa.lines, pa.lines_span[2], pa.lines_span[3], pa.sc.tri, pa.sc.tri + hgid,
                                    (uint32_t)sizeof(ShadeTri));
                     // inlined: 3 % faster than an out-of-line call once every load is global
-                    shade_hit_tab(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
-                              pa.max_depth, depth == nb - 1, bo, COUNT ? &tl_phase : nullptr);
+                    shade_hit_path<SIMPLE>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
+                                           pa.max_depth, depth == nb - 1, bo, COUNT ? &tl_phase : nullptr);
                     if (bo.emit) {
                         Lr.x += bo.e.x;
                         Lr.y += bo.e.y;
@@ -2450,11 +2469,14 @@ __device__ __forceinline__ void path_plain(const PathArgs &pa) {
 
 template <bool COUNT, bool TAB>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path(PathArgs pa) {
-    path_plain<COUNT, TAB, true>(pa);
+    // the product build: simple shading and the one-triangle leaf phase; the counting build: the general
+    // shading (and, as before, the general leaf phase), so a counted render cross-checks the two shaders
+    path_plain<COUNT, TAB, true, !COUNT>(pa);
 }
-template <bool TAB>
+// the general leaf phase with either shading; general shading always runs here
+template <bool TAB, bool SIMPLE>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_general(PathArgs pa) {
-    path_plain<false, TAB, false>(pa);
+    path_plain<false, TAB, false, SIMPLE>(pa);
 }
 
 __device__ __forceinline__ void path_park(uint32_t (*s_park)[kTraceBlock], uint32_t tid, const PathRay &r) {
@@ -2527,7 +2549,7 @@ struct DeferState {
     __device__ __forceinline__ bool running() const { return get(RUN, 1) != 0; }
 };
 
-template <bool COUNT, bool TAB>
+template <bool COUNT, bool TAB, bool SIMPLE>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_defer(PathArgs pa) {
     if (pa.gate && *pa.gate != pa.gate_want) return;  // the other candidate form runs (uniform: before any barrier)
     const TraceArgs &a = pa.t;
@@ -2635,7 +2657,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                         const V3 wo{-bitsf(s_park[3][tid]), -bitsf(s_park[4][tid]), -bitsf(s_park[5][tid])};
                         const int depth = s.depth();
                         Bounce bo;
-                        shade_hit_tab(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
+                        shade_hit_path<SIMPLE>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
                                   pa.max_depth, depth == nb - 1, bo);
                         if (bo.emit) {
                             Lr.x += bo.e.x;
@@ -2877,7 +2899,7 @@ struct SpecState {
     __device__ __forceinline__ uint32_t nh() const { return get(NH, 5); }
 };
 
-template <bool COUNT, bool TAB>
+template <bool COUNT, bool TAB, bool SIMPLE>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_spec(PathArgs pa) {
     if (pa.gate && *pa.gate != pa.gate_want) return;  // the other candidate form runs (uniform: before any barrier)
     const TraceArgs &a = pa.t;
@@ -2968,7 +2990,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 } else {
                     const V3 wo{-bitsf(s_park[3][tid]), -bitsf(s_park[4][tid]), -bitsf(s_park[5][tid])};
                     Bounce bo;
-                    shade_hit_tab(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth, pa.max_depth, depth == nb - 1, bo);
+                    shade_hit_path<SIMPLE>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth, pa.max_depth, depth == nb - 1, bo);
                     if (bo.emit) {
                         Lr.x += bo.e.x;
                         Lr.y += bo.e.y;
@@ -3728,31 +3750,44 @@ void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st)
 }
 // The persistent path kernel for (kind, count, tab).  The compiler emits the instantiations in the order
 // they are named here, which is the order the code object has always held them in.
+// The counting builds shade with the general build whatever `simple` says.  Of PATH_PLAIN's product builds
+// k_path<false, TAB> is simple shading with the one-triangle leaf phase (the name the committed traffic
+// profile is found by); every other pair of (leaf_one, simple) is a k_path_general, whose leaf phase finds
+// the same hits, so a forced k_path on a complex scene runs k_path_general<TAB, false>.
 using PathKernel = void (*)(PathArgs);
-static PathKernel path_kernel(int kind, bool count, bool tab, bool leaf_one = true) {
+static PathKernel path_kernel(int kind, bool count, bool tab, bool leaf_one, bool simple) {
     if (count && tab) {
-        if (kind == PATH_DEFER) return k_path_defer<true, true>;
-        if (kind == PATH_SPEC) return k_path_spec<true, true>;
+        if (kind == PATH_DEFER) return k_path_defer<true, true, false>;
+        if (kind == PATH_SPEC) return k_path_spec<true, true, false>;
         return k_path<true, true>;
     }
     if (count) {
-        if (kind == PATH_DEFER) return k_path_defer<true, false>;
-        if (kind == PATH_SPEC) return k_path_spec<true, false>;
+        if (kind == PATH_DEFER) return k_path_defer<true, false, false>;
+        if (kind == PATH_SPEC) return k_path_spec<true, false, false>;
         return k_path<true, false>;
     }
-    if (kind == PATH_SPEC) return tab ? k_path_spec<false, true> : k_path_spec<false, false>;
-    if (kind == PATH_DEFER) return tab ? k_path_defer<false, true> : k_path_defer<false, false>;
-    if (!leaf_one) return tab ? k_path_general<true> : k_path_general<false>;
+    if (kind == PATH_SPEC) {
+        if (simple) return tab ? k_path_spec<false, true, true> : k_path_spec<false, false, true>;
+        return tab ? k_path_spec<false, true, false> : k_path_spec<false, false, false>;
+    }
+    if (kind == PATH_DEFER) {
+        if (simple) return tab ? k_path_defer<false, true, true> : k_path_defer<false, false, true>;
+        return tab ? k_path_defer<false, true, false> : k_path_defer<false, false, false>;
+    }
+    if (!simple) return tab ? k_path_general<true, false> : k_path_general<false, false>;
+    if (!leaf_one) return tab ? k_path_general<true, true> : k_path_general<false, true>;
     return tab ? k_path<false, true> : k_path<false, false>;
 }
-void launch_path(bool count, int kind, bool tab, bool leaf_one, const PathArgs &a, uint32_t grid, hipStream_t st) {
+void launch_path(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathArgs &a, uint32_t grid,
+                 hipStream_t st) {
     if (grid == 0) return;
     if (tab && !path_tab_fits(a.sc.n_mats, a.sc.n_lights)) tab = false;  // the LDS copy must hold every record
-    hipLaunchKernelGGL(path_kernel(kind, count, tab, leaf_one), dim3(grid), dim3(kTraceBlock), 0, st, a);
+    hipLaunchKernelGGL(path_kernel(kind, count, tab, leaf_one, simple), dim3(grid), dim3(kTraceBlock), 0, st, a);
 }
-int path_blocks_per_cu(int kind, bool tab) {
+int path_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple) {
     int nb = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(kind, false, tab), kTraceBlock, 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(kind, false, tab, leaf_one, simple),
+                                                                      kTraceBlock, 0);
     if (e != hipSuccess || nb <= 0) nb = 1;
     return nb;
 }

@@ -652,6 +652,14 @@ int akr_hip_render_info(akr_hip_ctx *ctx, int32_t *lanes, int32_t *passes);
 #define AKR_FORM_PATH_DEFER 3
 #define AKR_FORM_PATH_SPEC 4
 int akr_hip_render_form(akr_hip_ctx *ctx, int32_t *form, int32_t *ordered);
+/* Which shading build the last path render ran (both give the same bits).  A persistent
+ * form's product build runs the simple one when the committed material and light tables hold constant
+ * Diffuse / Emissive only; its counting build, a persistent form on any other scene and the wavefront
+ * kernels run the general one.  AKR_SHADING_NONE: nothing rendered. */
+#define AKR_SHADING_NONE (-1)
+#define AKR_SHADING_GENERAL 0
+#define AKR_SHADING_SIMPLE 1
+int akr_hip_render_shading(akr_hip_ctx *ctx, int32_t *shading);
 /* The inputs of the last persistent render's form choice: its pixels per resident
  * lane x 1000, and the cost-ordering pilot's camera rays and their summed traversal steps; -1 when the
  * choice did not read the pilot (a forced form, no cost order, or a render too large for a tail form). */
