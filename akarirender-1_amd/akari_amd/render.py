@@ -27,6 +27,9 @@ PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm, with or without --den
 The session tracks the variance of every pixel's mean from its passes and each film is
 filtered by the variance-guided filter, whose colour stop follows how converged a pixel is.  One call is one
 batch, so the render has to run in passes; --aov then also writes PREFIX.variance.pfm.
+       ... --env FILE --env-path
+With an environment, --env-path sets library option "env_path" on every context: the persistent path
+kernel renders the scene where the render form rule takes it.  The image is the same.
 """
 from __future__ import annotations
 
@@ -101,9 +104,10 @@ class FilmPost:
 
 
 def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[FilmPost] = None,
-                 **build_kw) -> Tuple[np.ndarray, np.ndarray]:
+                 env_path: bool = False, **build_kw) -> Tuple[np.ndarray, np.ndarray]:
     """Render `sc` with its integrator node; returns the film (radiance [H,W,3], weight [H,W]).  With
-    `post`, the features and the filter run on the first device after the film is gathered."""
+    `post`, the features and the filter run on the first device after the film is gathered.
+    env_path: option "env_path" on every context (a choice of form under an environment, same bits)."""
     cs = scene.compile_scene(sc)
     w, h = (int(v) for v in sc.camera.resolution)
     it = sc.integrator
@@ -113,6 +117,7 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[
             scene.upload_scene(c, cs, **build_kw)
             if getattr(it, "mis", False):   # a session switch, read when the render starts
                 c.set_option("mis", 1)
+            c.set_option("env_path", 1 if env_path else 0)
         if isinstance(it, scene.AOIntegrator):
             if len(ctxs) != 1:
                 raise ValueError("the AO integrator renders on one device")
@@ -137,7 +142,8 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[
 
 def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optional[int] = None,
                              on_pass=None, time_budget: Optional[float] = None, checkpoint=None, resume=None,
-                             post: Optional[FilmPost] = None, **build_kw) -> Tuple[np.ndarray, np.ndarray, int]:
+                             post: Optional[FilmPost] = None, env_path: bool = False,
+                             **build_kw) -> Tuple[np.ndarray, np.ndarray, int]:
     """Render a Path scene in passes on one device; returns (radiance, weight, spp_done).
 
     pass_spp: samples per pass (default: each pass doubles the samples done); on_pass(spp_done,
@@ -161,6 +167,7 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
     with capi.HipContext(device) as ctx:
         scene.upload_scene(ctx, cs, **build_kw)
         ctx.set_option("mis", 1 if it.mis else 0)   # before the restore: a session reads it when it starts
+        ctx.set_option("env_path", 1 if env_path else 0)   # read at every render and continue; not in the checkpoint
         if post is not None:
             post.start(ctx)   # before the restore: an imported film is the tracker's first batch
             post.bind(tiles, w, h)
@@ -185,7 +192,7 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
 
 def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, min_spp: int = 16,
                           pass_spp: Optional[int] = None, on_pass=None, time_budget: Optional[float] = None,
-                          post: Optional[FilmPost] = None, **build_kw):
+                          post: Optional[FilmPost] = None, env_path: bool = False, **build_kw):
     """Render a Path scene adaptively on one device; returns (radiance, weight, info).  The integrator's
     spp is the cap; weight holds each pixel's sample count (progressive.render_adaptive)."""
     it = sc.integrator
@@ -197,6 +204,7 @@ def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, mi
     with capi.HipContext(device) as ctx:
         scene.upload_scene(ctx, cs, **build_kw)
         ctx.set_option("mis", 1 if it.mis else 0)
+        ctx.set_option("env_path", 1 if env_path else 0)
         tiles = _tiles(sc, it.tile_size)
         each = on_pass
         if post is not None:
@@ -271,6 +279,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--mis", action="store_true",
                     help="Path integrator: combine the light sample and the BSDF sample of direct lighting by the "
                          "power heuristic (multiple importance sampling); the scene's `mis` field does the same")
+    ap.add_argument("--env-path", action="store_true",
+                    help="with an environment: let the persistent path kernel render the scene where the render "
+                         "form rule takes it (library option env_path); the image is the same, bit for bit")
     ap.add_argument("--env-res", type=int, default=None, metavar="N",
                     help="resolution of the octahedral map made from a lat-long image, 1..2048")
     args = ap.parse_args(argv)
@@ -368,7 +379,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             per_pass = args.preview or args.time_budget is not None
             rad, wt, info = render_scene_adaptive(sc, args.adaptive, 0, min_spp=args.min_spp, pass_spp=args.pass_spp,
                                                   on_pass=show_adaptive if per_pass else None,
-                                                  time_budget=args.time_budget, post=post)
+                                                  time_budget=args.time_budget, post=post, env_path=args.env_path)
         except ValueError as e:
             ap.error(str(e))
         done = f"{info['spp_min']}..{info['spp_max']} ({info['samples']} samples in {info['passes']} passes)"
@@ -383,11 +394,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         try:
             rad, wt, done = render_scene_progressive(sc, 0, pass_spp=args.pass_spp, on_pass=show,
                                                      time_budget=args.time_budget, checkpoint=args.checkpoint,
-                                                     resume=args.resume, post=post)
+                                                     resume=args.resume, post=post, env_path=args.env_path)
         except progressive.CheckpointError as e:
             ap.error(str(e))
     else:
-        rad, wt = render_scene(sc, devices=list(range(args.gpus)), post=post)
+        rad, wt = render_scene(sc, devices=list(range(args.gpus)), post=post, env_path=args.env_path)
         done = sc.integrator.spp
     write_out(rad, wt)
     if args.aov is not None:

@@ -378,6 +378,11 @@ class HipPathTracer {
     void set_mis(const HipAccelerator &scene, bool on = true) const {
         check(scene.handle(), akr_hip_set_option(scene.handle(), "mis", on ? 1 : 0), "set_mis");
     }
+    // Under an environment light, let the persistent path kernel render where option "path" takes it (option
+    // "env_path", include/akr_hip.h): read at every render and continue; the same bits.
+    void set_env_path(const HipAccelerator &scene, bool on = true) const {
+        check(scene.handle(), akr_hip_set_option(scene.handle(), "env_path", on ? 1 : 0), "set_env_path");
+    }
     void render_variance(const HipAccelerator &scene, const Film &film, std::vector<float> &variance) const {
         variance.assign(4 * (size_t)film.width * film.height, 0.0f);
         check(scene.handle(), akr_hip_render_variance(scene.handle(), variance.data()), "render_variance");

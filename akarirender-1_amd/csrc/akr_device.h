@@ -377,4 +377,13 @@ struct PathArgs {
     uint32_t *state_out;           // per slot: the sampler state after the slot's last sample of this launch
 };
 
+// k_path_env (option env_path): k_path's arguments and the environment, after ShadeEnvArgs.  The record lies
+// in device memory behind one pointer and is read where the processing phase uses it: as 96 B of kernel
+// arguments its fields stayed in scalar registers across the traversal loop (81 spilled SGPRs and 2 spilled
+// VGPRs in the simple build; 45 and 0 this way)
+struct PathEnvArgs {
+    PathArgs p;
+    const AKR_GLOBAL EnvDev *env;
+};
+
 }  // namespace akr

@@ -225,6 +225,18 @@ struct akr_hip_ctx {
     EnvDev env{};
     DBuf<float4> d_env_map;
     DBuf<float> d_env_tab;  // marginal CDF, marginal pdf, conditional CDFs, conditional pdfs
+    // `env` itself on the device, for k_path's environment build, which reads it behind one pointer (option
+    // env_path); copied by the first such render after an upload, so nothing is allocated or
+    // copied while the option is off
+    DBuf<EnvDev> d_env_rec;
+    bool env_rec_stale = true;
+    const AKR_GLOBAL EnvDev *env_rec(hipStream_t st) {
+        if (env_rec_stale) {
+            d_env_rec.upload(&env, 1, st);
+            env_rec_stale = false;
+        }
+        return (const AKR_GLOBAL EnvDev *)d_env_rec.p;
+    }
     bool env_on() const { return env.n > 0; }
     const EnvDev &require_env() const {
         if (!env_on()) throw std::runtime_error("no environment light (akr_hip_upload_environment)");
@@ -377,6 +389,14 @@ struct akr_hip_ctx {
     // resident workgroups of the persistent path kernels' product builds [kind][tab][leaf_one][simple]: of the
     // kernel launch_path() launches for them
     uint32_t path_grid[3][2][2][2] = {};
+    // the same of k_path's environment builds [tab][leaf_one][simple] (launch_path_env), queried when option
+    // env_path first renders with one; never above the grid the overflow stacks are sized for
+    uint32_t path_env_grid[2][2][2] = {};
+    uint32_t env_grid(bool tab, bool leaf_one, bool simple) {
+        uint32_t &g = path_env_grid[tab][leaf_one][simple];
+        if (!g) g = std::min<uint32_t>((uint32_t)(n_cu * path_env_blocks_per_cu(tab, leaf_one, simple)), ovf_threads / kTraceBlock);
+        return g;
+    }
     // the render form rule is plan_path() in path_plan.h; its knobs are in `opt`
     // the last render's form inputs (akr_hip_render_form_inputs): pixels per lane x 1000, the pilot's
     // rays and their summed steps
@@ -811,6 +831,8 @@ struct akr_hip_ctx {
     // starts from its seed in every render) into the zeroed film, whose pixel probe d_pprobe then holds
     // each slot's closest-hit and shadow rays; the film is zeroed again for the render.  Nothing of it
     // reaches the context's statistics (scratch counters, no phase profile).
+    // With an environment (option env_path) the counting environment kernel runs, so the ray counts are those of
+    // the render the pilot ranks.
     void probe_render(const PathArgs &base, bool tab, uint32_t N, int S, hipStream_t ms) {
         if (d_pprobe.n < N) throw std::runtime_error("pilot probe buffer not sized");
         HIPCHK(hipMemsetAsync(d_owork.p, 0, kTraceWords * sizeof(uint32_t), ms));
@@ -825,8 +847,11 @@ struct akr_hip_ctx {
         pp.fault_test = 0;
         pp.state_in = pp.state_out = nullptr;
         const uint32_t grid = (uint32_t)std::max<uint64_t>(
-            1, std::min<uint64_t>(path_grid[PATH_PLAIN][tab][1][1], ((uint64_t)N + kTraceBlock - 1) / kTraceBlock));
-        launch_path(true, PATH_PLAIN, tab, leaf_one_kernel, false, pp, grid, ms);  // counting: the general shading
+            1, std::min<uint64_t>(env_on() ? env_grid(tab, true, true) : path_grid[PATH_PLAIN][tab][1][1],
+                                  ((uint64_t)N + kTraceBlock - 1) / kTraceBlock));
+        // counting: the general shading
+        if (env_on()) launch_path_env(true, tab, leaf_one_kernel, false, PathEnvArgs{pp, env_rec(ms)}, grid, ms);
+        else launch_path(true, PATH_PLAIN, tab, leaf_one_kernel, false, pp, grid, ms);
         HIPCHK(hipMemsetAsync(d_film.p, 0, (size_t)N * sizeof(float4), ms));
     }
 
@@ -1172,10 +1197,12 @@ struct akr_hip_ctx {
         // kernel measured faster there (textured hall 11.5 vs 16.0 ms per 4K spp)
         const bool use_path = opt.path_kernel == 1 || (opt.path_kernel == 2 && (int64_t)M <= opt.path_auto_pixels &&
                                                        (simple_shading || opt.path_auto_complex));
-        // an environment light is shaded by the wavefront's k_shade_env alone, whatever
-        // `path` says: the precedent exact_cull and a non-lean view set
+        // an environment light is shaded by the wavefront's k_shade_env, whatever `path`
+        // says: the precedent exact_cull and a non-lean view set; under option env_path it no longer decides,
+        // and render_path() runs k_path's environment build
         // and so does option "mis": its kernels are the wavefront's
-        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_on() && !mis_on) {
+        const bool env_wavefront = env_on() && !opt.env_path;
+        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_wavefront && !mis_on) {
             if (p.spp > 0) render_path(pass);
             last_passes = 1;
         } else {
@@ -1251,7 +1278,11 @@ struct akr_hip_ctx {
         in.subset = r.subset != nullptr;
         in.n_tris = n_tris();
         in.bvh_dev_bytes = bvh_dev_bytes;
-        for (int k = 0; k < 3; k++) in.grid[k] = path_grid[k][tab][leaf_one_kernel][simple];
+        // an environment (option env_path): only k_path has a build for it
+        const bool envp = env_on();
+        in.plain_only = envp;
+        for (int k = 0; k < 3; k++)
+            in.grid[k] = envp ? env_grid(tab, leaf_one_kernel, simple) : path_grid[k][tab][leaf_one_kernel][simple];
         in.block = kTraceBlock;
         const PathPlan pl = plan_path(in, opt);
         last_ppl1000 = pl.ppl1000;
@@ -1287,9 +1318,14 @@ struct akr_hip_ctx {
                 x.gate_want = (uint32_t)k;
             }
         }
+        const AKR_GLOBAL EnvDev *erec = envp ? env_rec(ms) : nullptr;  // copied before the timed launch, once per upload
         timed("path", ms, [&] {  // one timed record: a gated launch that exits at once adds microseconds
-            for (int k = 0; k < pl.n_launch; k++)
-                launch_path(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, simple, args[k], pl.launch[k].grid, ms);
+            for (int k = 0; k < pl.n_launch; k++) {
+                if (envp)
+                    launch_path_env(opt.count, tab, leaf_one_kernel, simple, PathEnvArgs{args[k], erec}, pl.launch[k].grid, ms);
+                else
+                    launch_path(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, simple, args[k], pl.launch[k].grid, ms);
+            }
         });
         HIPCHK(hipGetLastError());
         last_shading = simple ? AKR_SHADING_SIMPLE : AKR_SHADING_GENERAL;
@@ -1878,6 +1914,7 @@ int akr_hip_upload_environment(akr_hip_ctx *ctx, const akr_environment *e, const
         // no render of this context may still read the tables that are replaced here
         if (ctx->done_recorded) HIPCHK(hipEventSynchronize(ctx->ev_done));
         ctx->drop_session();
+        ctx->env_rec_stale = true;
         if (!rgb) {  // remove
             ctx->env = EnvDev{};
             return;

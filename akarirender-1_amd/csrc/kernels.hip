@@ -1324,11 +1324,12 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
 }
 
 // the persistent path kernels' call: the table's type deduced, the shading build named
-template <bool SIMPLE, class Tab>
+// ENV: with an environment light (option env_path): its branch of direct lighting, as k_shade_env's call
+template <bool SIMPLE, bool ENV = false, class Tab>
 __device__ __forceinline__ void shade_hit_path(const SceneDev &s, const Tab &tab, uint32_t gid, float u, float v, V3 wo,
                                                V3 beta, uint32_t &seed, int depth, int max_depth, bool last, Bounce &o,
-                                               unsigned long long *t_load = nullptr) {
-    shade_hit_tab<Tab, false, false, SIMPLE>(s, tab, gid, u, v, wo, beta, seed, depth, max_depth, last, o, t_load);
+                                               unsigned long long *t_load = nullptr, const EnvDev *env = nullptr) {
+    shade_hit_tab<Tab, ENV, false, SIMPLE>(s, tab, gid, u, v, wo, beta, seed, depth, max_depth, last, o, t_load, env);
 }
 
 __device__ __forceinline__ void shade_hit(const SceneDev &s, uint32_t gid, float u, float v, V3 wo, V3 beta,
@@ -2217,8 +2218,10 @@ constexpr int kParkSlots = 8;
 // ONE: the product leaf phase is path_leaf_masks (k_path); else path_leaf's general form for every wave
 // (k_path_general, the kernel of scenes whose leaves mostly hold several triangles: leaf_layout.h leaf_one_pays)
 // SIMPLE: shade_hit_tab's build for tables of constant Diffuse / Emissive (shade_simple.h)
-template <bool COUNT, bool TAB, bool ONE, bool SIMPLE>
-__device__ __forceinline__ void path_plain(const PathArgs &pa) {
+// ENV: the scene has an environment light (k_path_env, option env_path): the shading takes
+// its branch of direct lighting and a camera ray that leaves the scene sees the map, both as k_shade_env
+template <bool COUNT, bool TAB, bool ONE, bool SIMPLE, bool ENV = false>
+__device__ __forceinline__ void path_plain(const PathArgs &pa, const EnvDev *env = nullptr) {
     if (pa.gate && *pa.gate != pa.gate_want) return;  // the other candidate form runs (uniform: before any barrier)
     const TraceArgs &a = pa.t;
     __shared__ unsigned long long s_stack_mem[kStackLdsU64];
@@ -2303,6 +2306,15 @@ __device__ __forceinline__ void path_plain(const PathArgs &pa) {
             if (!busy && !done && fin) {
                 fin = false;
                 const uint32_t hgid = r.bgid;
+                // ENV: the record's address passes through an empty asm here, so its fields are loaded in this
+                // phase, where they are used, and not before the loop (where they stayed live across the
+                // traversal and spilled)
+                [[maybe_unused]] const EnvDev *envp = env;
+                if constexpr (ENV) {
+                    unsigned long long eb = (unsigned long long)env;
+                    asm volatile("" : "+s"(eb));
+                    envp = (const EnvDev *)(const AKR_GLOBAL EnvDev *)eb;
+                }
                 if (any) {  // shadow ray: NEE contribution when unoccluded (pathtracer.h:84-88)
                     if (hgid == kNoHit) {
                         Lr.x += scol.x;
@@ -2318,6 +2330,18 @@ __device__ __forceinline__ void path_plain(const PathArgs &pa) {
                         sample_end = true;
                     }
                 } else if (hgid == kNoHit) {  // on_miss: the sample ends
+                    if constexpr (ENV) {
+                        if (depth == 0) {  // a camera ray that leaves the scene sees the map; deeper misses add nothing
+                            const V3 d{bitsf(s_park[3][tid]), bitsf(s_park[4][tid]), bitsf(s_park[5][tid])};
+                            int ti, tj;
+                            float len;
+                            env_encode(envp->n, env_to_map(*envp, d), ti, tj, len);
+                            const V3 e = mul(beta, env_lookup(*envp, ti, tj));
+                            Lr.x += e.x;
+                            Lr.y += e.y;
+                            Lr.z += e.z;
+                        }
+                    }
                     sample_end = true;
                 } else {
                     const V3 wo{-bitsf(s_park[3][tid]), -bitsf(s_park[4][tid]), -bitsf(s_park[5][tid])};
@@ -2326,8 +2350,8 @@ __device__ __forceinline__ void path_plain(const PathArgs &pa) {
                         mark_lines(pa.lines, pa.lines_span[2], pa.lines_span[3], pa.sc.tri, pa.sc.tri + hgid,
                                    (uint32_t)sizeof(ShadeTri));
                     // inlined: 3 % faster than an out-of-line call once every load is global
-                    shade_hit_path<SIMPLE>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
-                                           pa.max_depth, depth == nb - 1, bo, COUNT ? &tl_phase : nullptr);
+                    shade_hit_path<SIMPLE, ENV>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
+                                                pa.max_depth, depth == nb - 1, bo, COUNT ? &tl_phase : nullptr, envp);
                     if (bo.emit) {
                         Lr.x += bo.e.x;
                         Lr.y += bo.e.y;
@@ -2477,6 +2501,16 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
 template <bool TAB, bool SIMPLE>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_general(PathArgs pa) {
     path_plain<false, TAB, false, SIMPLE>(pa);
+}
+// With an environment light (option env_path): the same two kernels over PathEnvArgs, the
+// environment's record read from device memory behind one pointer
+template <bool COUNT, bool TAB>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_env(PathEnvArgs ea) {
+    path_plain<COUNT, TAB, true, !COUNT, true>(ea.p, (const EnvDev *)ea.env);
+}
+template <bool TAB, bool SIMPLE>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_env_general(PathEnvArgs ea) {
+    path_plain<false, TAB, false, SIMPLE, true>(ea.p, (const EnvDev *)ea.env);
 }
 
 __device__ __forceinline__ void path_park(uint32_t (*s_park)[kTraceBlock], uint32_t tid, const PathRay &r) {
@@ -3787,6 +3821,27 @@ void launch_path(bool count, int kind, bool tab, bool leaf_one, bool simple, con
 int path_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple) {
     int nb = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(kind, false, tab, leaf_one, simple),
+                                                                      kTraceBlock, 0);
+    if (e != hipSuccess || nb <= 0) nb = 1;
+    return nb;
+}
+// The environment's kernels (option env_path): PATH_PLAIN's set, chosen as path_kernel() chooses, and named
+// after every kernel above so that those keep their places in the code object
+using PathEnvKernel = void (*)(PathEnvArgs);
+static PathEnvKernel path_env_kernel(bool count, bool tab, bool leaf_one, bool simple) {
+    if (count) return tab ? k_path_env<true, true> : k_path_env<true, false>;
+    if (!simple) return tab ? k_path_env_general<true, false> : k_path_env_general<false, false>;
+    if (!leaf_one) return tab ? k_path_env_general<true, true> : k_path_env_general<false, true>;
+    return tab ? k_path_env<false, true> : k_path_env<false, false>;
+}
+void launch_path_env(bool count, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid, hipStream_t st) {
+    if (grid == 0) return;
+    if (tab && !path_tab_fits(a.p.sc.n_mats, a.p.sc.n_lights)) tab = false;  // the LDS copy must hold every record
+    hipLaunchKernelGGL(path_env_kernel(count, tab, leaf_one, simple), dim3(grid), dim3(kTraceBlock), 0, st, a);
+}
+int path_env_blocks_per_cu(bool tab, bool leaf_one, bool simple) {
+    int nb = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_env_kernel(false, tab, leaf_one, simple),
                                                                       kTraceBlock, 0);
     if (e != hipSuccess || nb <= 0) nb = 1;
     return nb;

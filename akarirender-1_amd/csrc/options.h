@@ -26,6 +26,11 @@ struct Options {
     // of the next-event sample and the BSDF sample; the render takes the wavefront form.
     // Off: nothing is allocated, and every launch is the one it was
     bool mis = false;
+    // option "env_path" (default 0, read at every render and continue, like "path"): an environment light no
+    // longer forces the wavefront form; where the rule of "path" takes a persistent kernel, k_path's environment
+    // build renders the scene (k_path_env), bit for bit what k_shade_env gives.
+    // Off: every launch is the one it was
+    bool env_path = false;
 
     // The render form of a constant-shading scene.  A "tail form"
     // (k_path_spec, or k_path_defer when path_spec is 0) pays where k_path's launch would end on a few
@@ -254,6 +259,11 @@ inline std::string set_option(Options &o, const char *key, int64_t value) {
     if (key && strcmp(key, "mis") == 0) {  // the same kind of switch
         if (value != 0 && value != 1) return "mis must be in [0, 1]";
         o.mis = value == 1;
+        return {};
+    }
+    if (key && strcmp(key, "env_path") == 0) {  // a choice of form under an environment
+        if (value != 0 && value != 1) return "env_path must be in [0, 1]";
+        o.env_path = value == 1;
         return {};
     }
     const OptionRow *r = find_option(key);

@@ -23,6 +23,10 @@ struct PathPlanIn {
     uint64_t bvh_dev_bytes = 0;   // the uploaded wide nodes + leaf blob
     uint32_t grid[3] = {0, 0, 0}; // resident workgroups of each kernel form [kind], for the render's `tab`
     uint32_t block = 256;         // threads per workgroup of the path kernels
+    // only PATH_PLAIN exists for this render (an environment light under option env_path):
+    // one ungated k_path launch whatever path_defer / path_spec and the cache rule say; the pilot, the cost
+    // order, subset lists, path_grid_pct and path_prio apply as for k_path
+    bool plain_only = false;
 };
 
 // which list a launch fetches its slots through
@@ -69,10 +73,12 @@ inline PathPlan plan_path(const PathPlanIn &in, const Options &o) {
     const int64_t ppl1000 = (int64_t)((M * 1000 + lanes / 2) / lanes);
     pl.ppl1000 = ppl1000;
     pl.order_min_spp = order_min_spp(o, N);
-    const bool forced = o.path_spec == 1 || o.path_defer != 2;
+    // plain_only: the form is given, as if path_defer 0 / path_spec 0 had forced k_path
+    const int path_spec = in.plain_only ? 0 : o.path_spec, path_defer = in.plain_only ? 0 : o.path_defer;
+    const bool forced = path_spec == 1 || path_defer != 2;
     // the pilot can rank pixels for every form (path_order 2), or for k_path only (1)
     pl.pilot = o.path_order != 0 && !in.subset && in.spp >= pl.order_min_spp && N >= 2 &&
-               (o.path_order == 2 || (!forced || (o.path_spec != 1 && o.path_defer == 0)));
+               (o.path_order == 2 || (!forced || (path_spec != 1 && path_defer == 0)));
     // a continued render ranks by the camera-ray pilot: the path pilot renders into the film
     pl.path_pilot = pl.pilot && o.path_order_pilot_spp > 0 && !in.cont;
     // the rule: its size and scene tests, then the camera-ray pilot's mean steps
@@ -80,19 +86,19 @@ inline PathPlan plan_path(const PathPlanIn &in, const Options &o) {
     const bool tris_ok = o.path_defer_min_tris == 0 || (int64_t)in.n_tris >= o.path_defer_min_tris;
     // the BVH's device bytes against the Infinity Cache share: a cache-resident
     // tree takes k_path_defer at any size, a larger one k_path_spec up to path_tail_ppl10
-    const bool cache_resident = o.path_spec != 1 && in.max_depth <= 8 && in.bvh_dev_bytes <= (uint64_t)o.path_cache_mb << 20;
-    const bool size_tail = o.path_spec == 2 ? (o.path_spec_pixels > 0 ? (int64_t)N <= o.path_spec_pixels : size_ok)
-                                            : (o.path_defer_pixels > 0 ? (int64_t)N <= o.path_defer_pixels : size_ok);
+    const bool cache_resident = path_spec != 1 && in.max_depth <= 8 && in.bvh_dev_bytes <= (uint64_t)o.path_cache_mb << 20;
+    const bool size_tail = path_spec == 2 ? (o.path_spec_pixels > 0 ? (int64_t)N <= o.path_spec_pixels : size_ok)
+                                          : (o.path_defer_pixels > 0 ? (int64_t)N <= o.path_defer_pixels : size_ok);
     pl.want_steps = !forced && o.path_order == 2 && pl.pilot && !pl.path_pilot && tris_ok && (cache_resident || size_tail);
     if (pl.want_steps) pl.pilot_rays = (int64_t)((N + (1u << o.path_order_sub) - 1) >> o.path_order_sub);
     // The rule's tail test reads the pilot's step sum, which is on the device: both candidates are
     // launched, and each exits at once unless the gate word names it
     const int tail_kind = cache_resident ? PATH_DEFER
-                                         : (o.path_spec == 2 ? PATH_SPEC : (in.max_depth <= 8 ? PATH_DEFER : PATH_PLAIN));
+                                         : (path_spec == 2 ? PATH_SPEC : (in.max_depth <= 8 ? PATH_DEFER : PATH_PLAIN));
     pl.gated = pl.want_steps && tail_kind != PATH_PLAIN;
     int kind = PATH_PLAIN;
-    if (o.path_spec == 1) kind = PATH_SPEC;
-    else if (o.path_defer == 1 && in.max_depth <= 8) kind = PATH_DEFER;
+    if (path_spec == 1) kind = PATH_SPEC;
+    else if (path_defer == 1 && in.max_depth <= 8) kind = PATH_DEFER;
 
     // one candidate's grid and fetch order
     auto configure = [&](int k) {

@@ -235,7 +235,13 @@ int akr_hip_set_option(akr_hip_ctx *ctx, const char *key, int64_t value);
  * other value is refused) makes direct lighting the power-heuristic combination of the next-event sample and the
  * BSDF sample the extension ray already is.  No draw and no ray is added: every slot's sampler
  * state and ray counts are those of a render without it.  The render takes the wavefront form whatever "path"
- * says, and akr_hip_render_form reports it.  The AO integrator ignores it. */
+ * says, and akr_hip_render_form reports it.  The AO integrator ignores it.
+ * And a choice of form: "env_path" (0 or 1, default 0; read at every render and continue, like "path"; any other
+ * value is refused).  An environment light keeps the wavefront form unless it is 1; with it on, "path" decides as
+ * it does without an environment, and where it takes a persistent kernel, k_path's environment build renders the
+ * scene (only k_path has one: "path_defer" and "path_spec" are not consulted).  The result is the
+ * wavefront's bit for bit; akr_hip_render_form reports k_path.  "mis", exact_cull, "wide" 0 and a view outside the
+ * lean test's bounds keep the wavefront as before.  Without an environment it changes nothing. */
 
 int akr_hip_upload_mesh(akr_hip_ctx *ctx, const float *vertices, uint64_t n_vertices,
                         const int32_t *indices, const float *normals, const float *texcoords,
