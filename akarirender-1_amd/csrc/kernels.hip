@@ -259,13 +259,25 @@ __device__ __forceinline__ float ubyte(uint32_t w, int k) {  // v_cvt_f32_ubyte{
 // or continues, bit 1 sp + 4 > kStackLds, bit 2 sp + pushes > kStackLds.  `entered` (k_path's product
 // iteration): receives pm, so that the caller tests "no slot entered" on a register of its own instead
 // of on a predicate merged across the visit's branch.
-template <bool ANY, bool NOPOP = false, bool FIT = false>
+// TRIM (k_path's product iteration): the same entries at the same rows and the same
+// `cur` in fewer vector instructions.  A pushed slot's row is sp + popc((rest >> 1) >> pos) (one shift
+// of `rest` for all four slots); "slot k is pushed" is the one-bit signed field of `rest` at pos[k]
+// (0 or ~0) and selects between the row's address and `dead` bitwise, with no compare; the pair
+// (ref, t) goes out as the two dwords of one LDS instruction, so no register pair is assembled; the
+// continuing slot is picked by the same one-bit fields of pm's lowest set bit; and the octant's order
+// byte is one byte permute of the two order words (selector dpos: bytes 0..3 the low word's, 4..7 the
+// high word's; the bytes above it are never read).
+__device__ __forceinline__ void lds_put_pair(uint32_t addr, uint32_t lo, uint32_t hi) {
+    asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" ::"v"(addr), "v"(lo), "v"(hi) : "memory");
+}
+template <bool ANY, bool NOPOP = false, bool FIT = false, bool TRIM = false>
 __device__ __forceinline__ bool wide_order_push(uint32_t order_lo, uint32_t order_hi, uint32_t dpos, const float (&t)[4],
                                                 const bool (&hit)[4], const uint32_t (&ref)[4], uint32_t &cur, float lim,
                                                 lds_u64 *s_stack, glb_u64 *ovf, uint32_t ovf_threads, uint32_t tid,
                                                 uint32_t gtid, int &sp, lds_u64 *dead = nullptr,
                                                 uint32_t *info = nullptr, uint32_t *entered = nullptr) {
-    const uint32_t perm = ((dpos & 4u) ? order_hi : order_lo) >> ((dpos & 3u) << 3);
+    const uint32_t perm = TRIM ? __builtin_amdgcn_perm(order_hi, order_lo, dpos)
+                               : ((dpos & 4u) ? order_hi : order_lo) >> ((dpos & 3u) << 3);
     const uint32_t pos[4] = {perm & 3u, (perm >> 2) & 3u, (perm >> 4) & 3u, (perm >> 6) & 3u};
     uint32_t pm = 0;  // entered slots, by position
 #pragma unroll
@@ -282,6 +294,43 @@ __device__ __forceinline__ bool wide_order_push(uint32_t order_lo, uint32_t orde
     // wave-uniform: no exec-mask split in the common case
     const bool all_lds = FIT ? __ballot(sp + (int)__popc(rest) > kStackLds) == 0 : __ballot(sp + 4 > kStackLds) == 0;
     // FIT: the straight-line push is the fall-through (> 98 % of k_path's pushing iterations)
+    if constexpr (TRIM) {
+        static_assert(FIT, "the trimmed push writes the unpushed slots to `dead`");
+        if (__builtin_expect(all_lds, 1)) {
+            const uint32_t rest1 = rest >> 1;
+            const uint32_t lane_row0 = (uint32_t)(uintptr_t)(s_stack + tid), dead_at = (uint32_t)(uintptr_t)dead;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t push = (uint32_t)__builtin_amdgcn_sbfe((int)rest, pos[k], 1u);  // 0 or ~0
+                const uint32_t row = (uint32_t)sp + __popc(rest1 >> pos[k]);
+                const uint32_t at = lane_row0 + row * (uint32_t)(kTraceBlock * sizeof(unsigned long long));
+                lds_put_pair((at & push) | (dead_at & ~push), ref[k], __float_as_uint(t[k]));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if ((rest >> pos[k]) & 1u) {
+                    const int e = sp + (int)__popc(rest >> (pos[k] + 1u));
+                    const unsigned long long v = (unsigned long long)ref[k] | ((unsigned long long)__float_as_uint(t[k]) << 32);
+                    if (e < kStackLds) lds_put(s_stack, e, tid, v);
+                    else ovf[(size_t)(e - kStackLds) * ovf_threads + gtid] = v;
+                }
+            }
+        }
+        sp += (int)__popc(rest);
+        // pm != 0 here, so some slot stands at the first entered position: slot 0 unless a later one does
+        // (bitwise selects on the one-bit signed field, as the push: a select on "pos[k] == position"
+        // is turned into an indexed read of ref[], a private array in scratch)
+        const uint32_t first = pm ^ rest;
+        uint32_t c = ref[0];
+#pragma unroll
+        for (int k = 1; k < 4; k++) {
+            const uint32_t is = (uint32_t)__builtin_amdgcn_sbfe((int)first, pos[k], 1u);  // 0 or ~0
+            c = (ref[k] & is) | (c & ~is);
+        }
+        cur = c;
+        return false;
+    }
     if (FIT ? __builtin_expect(all_lds, 1) : all_lds) {
         // all in LDS: four unconditional writes, no exec-mask branches; a slot that is not pushed
         // writes entry sp + 3, which lies above the new top (sp grows by at most 3) and is dead
@@ -383,7 +432,29 @@ __device__ __forceinline__ WideNode wide_load(const float4 *wn, uint32_t cur) {
     return nd;
 }
 
-template <bool ANY, bool NOPOP = false, bool FIT = false>
+// The same IEEE maximum / minimum as fmaxf / fminf on numbers (no operand of the lean test is a NaN),
+// written as the instruction: the compiler otherwise re-canonicalises the loop-invariant tmin and lim
+// (v_max_f32 x, x) on every visit, since they reach the visit's block from outside it.
+__device__ __forceinline__ float max3_raw(float a, float b, float c, float d) {  // max(a, b, max(c, d))
+    float m, r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(c), "v"(d));
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(m));
+    return r;
+}
+__device__ __forceinline__ float min3_raw(float a, float b, float c, float d) {  // min(a, b, min(c, d))
+    float m, r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(m) : "v"(c), "v"(d));
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(m));
+    return r;
+}
+
+// TRIM (k_path's product iteration): the same visit in fewer vector instructions.
+//  - `tmaxp` is lim = min(best, tmaxp), formed by the caller once per traversal phase (best does not
+//    change inside it), and the push is wide_order_push's TRIM form.
+//  - The slot bounds stay v_cvt_f32_ubyte + v_fma_f32: a byte permute and a mixed-precision fma on f16
+//    subnormals need 36 instead of 48 instructions but issue more slowly (tools/experiments/visit_mix.patch).
+constexpr bool kTrimMinMax = true, kTrimPush = true;  // tools/experiments/visit_no_*.patch
+template <bool ANY, bool NOPOP = false, bool FIT = false, bool TRIM = false>
 __device__ __forceinline__ int visit_wide_lean_node(const WideNode &nd, uint32_t &cur, V3 o, uint32_t dpos, V3 invd,
                                                     float tmin, float tmaxp, float best, lds_u64 *s_stack, glb_u64 *ovf,
                                                     uint32_t ovf_threads, uint32_t tid, uint32_t gtid, int &sp,
@@ -407,7 +478,7 @@ __device__ __forceinline__ int visit_wide_lean_node(const WideNode &nd, uint32_t
     const uint32_t qnx = px ? qa.x : qa.y, qfx = px ? qa.y : qa.x;
     const uint32_t qny = py ? qa.z : qa.w, qfy = py ? qa.w : qa.z;
     const uint32_t qnz = pz ? qb.x : qb.y, qfz = pz ? qb.y : qb.x;
-    const float lim = ANY ? tmaxp : fminf(best, tmaxp);
+    const float lim = ANY || TRIM ? tmaxp : fminf(best, tmaxp);
     float t[4];
     bool hit[4];
     uint32_t ref[4] = {c.x, c.y, c.z, c.w};
@@ -416,14 +487,15 @@ __device__ __forceinline__ int visit_wide_lean_node(const WideNode &nd, uint32_t
         const float nx = __builtin_fmaf(ubyte(qnx, k), scx, nox), fx = __builtin_fmaf(ubyte(qfx, k), scx, fox);
         const float ny = __builtin_fmaf(ubyte(qny, k), scy, noy), fy = __builtin_fmaf(ubyte(qfy, k), scy, foy);
         const float nz = __builtin_fmaf(ubyte(qnz, k), scz, noz), fz = __builtin_fmaf(ubyte(qfz, k), scz, foz);
-        const float tk = fmaxf(fmaxf(nx, ny), fmaxf(nz, tmin));
-        const float m1 = fminf(fminf(fx, fy), fminf(fz, lim));
+        constexpr bool RAW = TRIM && kTrimMinMax;
+        const float tk = RAW ? max3_raw(nx, ny, nz, tmin) : fmaxf(fmaxf(nx, ny), fmaxf(nz, tmin));
+        const float m1 = RAW ? min3_raw(fx, fy, fz, lim) : fminf(fminf(fx, fy), fminf(fz, lim));
         t[k] = tk;
         hit[k] = ref[k] != AKR_CHILD_EMPTY && tk <= m1;
     }
     const int tested = (c.x != AKR_CHILD_EMPTY) + (c.y != AKR_CHILD_EMPTY) + (c.z != AKR_CHILD_EMPTY) +
                        (c.w != AKR_CHILD_EMPTY);
-    const bool np = wide_order_push<ANY, NOPOP, FIT>(qb.z, qb.w, dpos, t, hit, ref, cur, ANY ? tmaxp : best, s_stack, ovf,
+    const bool np = wide_order_push<ANY, NOPOP, FIT, TRIM && kTrimPush>(qb.z, qb.w, dpos, t, hit, ref, cur, ANY ? tmaxp : best, s_stack, ovf,
                                                      ovf_threads, tid, gtid, sp, dead, push_info, entered);
     if (NOPOP) *need_pop = np;
     return tested;
@@ -1726,13 +1798,14 @@ __device__ __forceinline__ void path_traverse_masks(unsigned long long bm, PathR
                                                     uint32_t pop_keep, uint32_t pop_rounds, lds_u64 *dead) {
     static_assert(EXIT >= 0 && EXIT < 64, "the exit test below counts a searching lane without a holder as 65");
     PathCount none;
+    const float lim = fminf(r.best, r.tmaxp);  // the visit's exit bound: r.best is constant across the call
     while (true) {
         uint32_t pm = 1u;  // the visit's entered slots; a lane that does not visit enters "one"
         [[maybe_unused]] bool np;
         if (in_mask(bm & mask_of(is_internal(r.cur)))) {
             const WideNode nd = wide_load(wn, r.cur);
-            visit_wide_lean_node<false, true, true>(nd, r.cur, r.o, r.dpos, r.invd, r.tmin, r.tmaxp, r.best, s_stack, ovf,
-                                                    ovf_threads, tid, gtid, r.sp, &np, dead, nullptr, &pm);
+            visit_wide_lean_node<false, true, true, true>(nd, r.cur, r.o, r.dpos, r.invd, r.tmin, lim, r.best, s_stack,
+                                                          ovf, ovf_threads, tid, gtid, r.sp, &np, dead, nullptr, &pm);
         }
         // (the empty asm keeps pm a register: the compiler otherwise threads the compare back through the
         // branch into a merged predicate, whose ballot is the pair above)
