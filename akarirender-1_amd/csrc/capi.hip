@@ -25,7 +25,9 @@
 #include "options.h"
 #include "leaf_layout.h"
 #include "path_plan.h"
+#include "session.h"
 #include "shade_simple.h"
+#include "tile_layout.h"
 
 using namespace akr;
 
@@ -245,57 +247,26 @@ struct akr_hip_ctx {
 
     // path / queue buffers
     size_t cap = 0;
-    // The last render's tile list, clipped, non-empty tiles only: (x0, y0, width, first slot).  The
-    // pixel list is expanded from it on the device (k_expand_pixels); the host copy h_pixel is built
-    // only for the host-side merges that need it (host_pixels()).
-    std::vector<uint4> h_tiles;
-    uint64_t n_pix_last = 0;
+    // The last render's tiles and slot count (tile_layout.h).  The pixel list is expanded from them on the
+    // device (k_expand_pixels); the host copy h_pixel is built only for the host-side merges that need it
+    // (host_pixels()).
+    TileLayout lay;
     DBuf<uint4> d_tiles;
-    // The session: the last path render, which akr_hip_render_continue extends.  Its
-    // slots are h_tiles / d_pixel, its sampler states d_seed (`seeded`: they hold the state after each
-    // slot's last sample; false after a render of 0 spp, whose slots start from x + y * width) and its
-    // sums d_film.  Every render starts by dropping it (setup_pixels); so do scene, tree and camera changes.
-    struct Session {
-        bool valid = false, seeded = false;
-        uint64_t n = 0;
-        int32_t spp_done = 0, max_depth = 0, flags = 0;
-        float ray_clamp = 0.0f;
-        // Slots that hold different sample counts (masked continues): spp_done is then the
-        // largest count, spp_min the smallest, and d_count holds every slot's expected count
-        bool uniform = true;
-        int32_t spp_min = 0;
-        // the last adaptive render's strips, for akr_hip_adaptive_error (0: none)
-        uint64_t n_strips = 0;
-        // an adaptive render in progress (akr_hip_adaptive_begin / _step): every active strip holds
-        // `total` samples, `m` slots are active; a continue that draws samples ends it (on = false)
-        struct Adaptive {
-            bool on = false, more = false, some_stopped = false;
-            int32_t cap = 0, pass_spp = 0, total = 0;
-            float threshold = 0.0f;
-            uint32_t m = 0;
-            akr_adaptive_info info{};
-        } ad;
-    } session;
+    static_assert(sizeof(TileRec) == sizeof(uint4) && alignof(TileRec) == alignof(uint4) && offsetof(TileRec, x0) == offsetof(uint4, x) &&
+                      offsetof(TileRec, y0) == offsetof(uint4, y) && offsetof(TileRec, width) == offsetof(uint4, z) &&
+                      offsetof(TileRec, first) == offsetof(uint4, w),
+                  "k_expand_pixels reads a TileRec as a uint4");
+    // `l`'s tiles into `d` and every slot's pixel into `pixel`, on `st`
+    static void expand_layout(const TileLayout &l, DBuf<uint4> &d, uint32_t *pixel, hipStream_t st) {
+        d.upload(reinterpret_cast<const uint4 *>(l.tiles.data()), l.tiles.size(), st);
+        launch_expand_pixels(d.p, (uint32_t)l.tiles.size(), (uint32_t)l.n, pixel, st);
+    }
+    // The session (session.h): the last path render, which akr_hip_render_continue extends.
+    // Its slots are lay / d_pixel, its sampler states d_seed and its sums d_film.  Every render starts by
+    // dropping it (setup_pixels); so do scene, tree and camera changes.
+    Session session;
     void drop_session() { session.valid = false; }
-    const Session &require_session() const {
-        if (!session.valid)
-            throw std::runtime_error("no render session to continue (start one with akr_hip_render, akr_hip_render_device "
-                                     "or akr_hip_render_state_import; scene, tree and camera changes and other renders end it)");
-        return session;
-    }
-    void open_session(const akr_pt_params &p, uint64_t N, int32_t spp_done, bool seeded) {
-        session.valid = true;
-        session.seeded = seeded;
-        session.n = N;
-        session.spp_done = spp_done;
-        session.max_depth = p.max_depth;
-        session.flags = p.flags;
-        session.ray_clamp = p.ray_clamp;
-        session.uniform = true;
-        session.spp_min = spp_done;
-        session.n_strips = 0;
-        session.ad = Session::Adaptive{};
-    }
+    const Session &require_session() const { return akr::require_session(session); }
     // Adaptive sampling: the active-slot list of a subset pass and its compaction
     // scratch, the per-slot expected counts of a non-uniform session, and the convergence test's
     // snapshot, slot mask and per-strip results
@@ -897,26 +868,15 @@ struct akr_hip_ctx {
         if (!cam_set) throw std::runtime_error("camera not set (call akr_hip_set_camera)");
         if (n_tiles < 0 || (n_tiles > 0 && !tiles)) throw std::runtime_error("invalid tile list");
         drop_session();
-        h_tiles.clear();
         h_pixel_ok = false;
-        uint64_t N = 0;
-        for (int k = 0; k < n_tiles; k++) {
-            const int x0 = std::max(0, tiles[k].x0), y0 = std::max(0, tiles[k].y0);
-            const int x1 = std::min(cam.width, tiles[k].x1), y1 = std::min(cam.height, tiles[k].y1);
-            if (x1 <= x0 || y1 <= y0) continue;
-            if (N >= (1ull << 31)) break;  // rejected below
-            h_tiles.push_back(make_uint4((uint32_t)x0, (uint32_t)y0, (uint32_t)(x1 - x0), (uint32_t)N));
-            N += (uint64_t)(x1 - x0) * (uint64_t)(y1 - y0);
-        }
-        if (N >= (1ull << 31)) throw std::runtime_error("too many pixels in one render call");
+        lay = layout_tiles(tiles, n_tiles, cam.width, cam.height, "render call");
+        const uint64_t N = lay.n;
         serialize(st);
         ensure_capacity(N);  // before any upload: a reallocation drops contents
         d_counts.reserve(2 * n_count_words);  // two pass parities
-        n_pix_last = N;
         if (N == 0) return 0;
         ensure_side_stream();
-        d_tiles.upload(h_tiles.data(), h_tiles.size(), st);
-        launch_expand_pixels(d_tiles.p, (uint32_t)h_tiles.size(), (uint32_t)N, d_pixel.p, st);
+        expand_layout(lay, d_tiles, d_pixel.p, st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(d_film.p, 0, N * sizeof(float4), st));
         fork_streams(st);
@@ -935,7 +895,7 @@ struct akr_hip_ctx {
     uint64_t resume_pixels(size_t n_count_words, hipStream_t st) {
         const uint64_t N = require_session().n;
         require_ready();
-        if (N != n_pix_last || N > cap) throw std::runtime_error("render session: the slot buffers changed");
+        if (N != lay.n || N > cap) throw std::runtime_error("render session: the slot buffers changed");
         serialize(st);
         d_counts.reserve(2 * n_count_words);  // two pass parities
         if (N == 0) return 0;
@@ -946,17 +906,8 @@ struct akr_hip_ctx {
 
     // The last render's pixel list on the host (slot order), for the host-side film merges
     const std::vector<uint32_t> &host_pixels() {
-        if (!h_pixel_ok) {
-            h_pixel.resize(n_pix_last);
-            for (const uint4 &t : h_tiles) {
-                const uint64_t end = &t == &h_tiles.back() ? n_pix_last : (&t)[1].w;
-                for (uint64_t i = t.w; i < end; i++) {
-                    const uint32_t local = (uint32_t)(i - t.w);
-                    h_pixel[i] = (t.x + local % t.z) | ((t.y + local / t.z) << 16);
-                }
-            }
-            h_pixel_ok = true;
-        }
+        if (!h_pixel_ok) slot_pixels(lay, h_pixel);
+        h_pixel_ok = true;
         return h_pixel;
     }
 
@@ -1044,15 +995,12 @@ struct akr_hip_ctx {
         const uint64_t N = require_session().n;
         if (m == 0 || spp == 0) return;
         if (m > N) throw std::runtime_error("render session: more active slots than slots");
-        // the 2^24 cap applies to the largest resulting count; refused before anything changes
-        if (s.uniform) {
-            if ((int64_t)s.spp_done + spp > kSessionSppCap) throw_cap(s.spp_done, spp);
-        } else if ((int64_t)s.spp_done + spp > kSessionSppCap) {  // near the cap only: the largest count among the listed slots
-            uint32_t lo, hi;
+        uint32_t lo, hi;
+        if (cap_needs_largest(s, spp)) {  // near the cap only: the largest count among the listed slots
             count_range(true, m, st, lo, hi);
-            if ((int64_t)hi + spp > kSessionSppCap) throw_cap((int32_t)hi, spp);
+            check_cap(hi, spp);
         }
-        const akr_pt_params p = session_params(spp);
+        const akr_pt_params p = session_params(s, spp);
         if (!s.seeded) {  // no sample drawn yet: the slots left out keep their start state x + y * width
             launch_init_seed(d_pixel.p, (uint32_t)N, cam.width, d_seed.p, st);
             s.seeded = true;
@@ -1066,44 +1014,15 @@ struct akr_hip_ctx {
             }
             render(p, nullptr, 0, st, true, d_active.p, m);
         }
-        if (s.uniform && m == N) {
-            s.spp_done += spp;
-            s.spp_min = s.spp_done;
-            return;
-        }
+        const SlotCounts counts = advance_subset(s, m, spp);
+        if (counts == SlotCounts::None) return;
         launch_count_add(d_count.p, m == N ? nullptr : d_active.p, m, (uint32_t)spp, st);
         HIPCHK(hipGetLastError());
-        if (s.uniform) {
-            s.uniform = false;
-            s.spp_min = s.spp_done;
-            s.spp_done += spp;
-        } else if (range) {
-            uint32_t lo, hi;
+        if (counts == SlotCounts::AddAndRead && range) {
             count_range(false, (uint32_t)N, st, lo, hi);
-            s.spp_min = (int32_t)lo;
-            s.spp_done = (int32_t)hi;
+            set_range(s, lo, hi);
         }
     }
-    static constexpr int32_t kSessionSppCap = 1 << 24;  // a slot's weight is an f32 count of its samples: exact up to 2^24
-    // a call refused before anything changed: the session stays as it was
-    struct Refused : std::runtime_error {
-        using std::runtime_error::runtime_error;
-    };
-    [[noreturn]] static void throw_cap(int32_t have, int32_t spp) {
-        throw Refused("render session: " + std::to_string(have) + " + " + std::to_string(spp) +
-                                 " samples per slot exceed 2^24 (the weight is an f32 count)");
-    }
-    // the session's parameters with `spp` more samples
-    akr_pt_params session_params(int32_t spp) const {
-        const Session &s = require_session();
-        akr_pt_params p{};
-        p.spp = spp;
-        p.max_depth = s.max_depth;
-        p.ray_clamp = s.ray_clamp;
-        p.flags = s.flags;
-        return p;
-    }
-
     // host waits for both internal streams (before a DMA read-back of the film)
     void host_join() {
         if (side) HIPCHK(hipStreamSynchronize(side));
@@ -1536,8 +1455,7 @@ struct akr_hip_ctx {
     // tile list, pixel list, chain states and accumulators, and borrows only the ray and hit queues (when
     // they are large enough: growing them would reallocate the session's film with them), the traversal
     // overflow stack and the standalone trace's fetch counters.
-    std::vector<uint4> ft_tiles;
-    uint64_t ft_n = 0;
+    TileLayout ft_lay;
     DBuf<uint4> d_ft_tiles;
     DBuf<uint32_t> d_ft_pixel, d_ft_seed;
     DBuf<float4> d_ft_acc, d_ft_ray, d_ft_hit;
@@ -1551,18 +1469,8 @@ struct akr_hip_ctx {
         require_ready();
         if (!cam_set) throw std::runtime_error("camera not set (call akr_hip_set_camera)");
         if (n_tiles < 0 || (n_tiles > 0 && !tiles)) throw std::runtime_error("invalid tile list");
-        ft_tiles.clear();
-        uint64_t N = 0;
-        for (int k = 0; k < n_tiles; k++) {  // clipped, non-empty tiles in order, as setup_pixels lays them out
-            const int x0 = std::max(0, tiles[k].x0), y0 = std::max(0, tiles[k].y0);
-            const int x1 = std::min(cam.width, tiles[k].x1), y1 = std::min(cam.height, tiles[k].y1);
-            if (x1 <= x0 || y1 <= y0) continue;
-            if (N >= (1ull << 31)) break;  // rejected below
-            ft_tiles.push_back(make_uint4((uint32_t)x0, (uint32_t)y0, (uint32_t)(x1 - x0), (uint32_t)N));
-            N += (uint64_t)(x1 - x0) * (uint64_t)(y1 - y0);
-        }
-        if (N >= (1ull << 31)) throw std::runtime_error("too many pixels in one feature pass");
-        ft_n = N;
+        ft_lay = layout_tiles(tiles, n_tiles, cam.width, cam.height, "feature pass");  // as setup_pixels lays them out
+        const uint64_t N = ft_lay.n;
         serialize(st);
         if (N == 0) {
             mark_done(st);
@@ -1578,8 +1486,7 @@ struct akr_hip_ctx {
             rays = d_ft_ray.p;
             hits = d_ft_hit.p;
         }
-        d_ft_tiles.upload(ft_tiles.data(), ft_tiles.size(), st);
-        launch_expand_pixels(d_ft_tiles.p, (uint32_t)ft_tiles.size(), (uint32_t)N, d_ft_pixel.p, st);
+        expand_layout(ft_lay, d_ft_tiles, d_ft_pixel.p, st);
         HIPCHK(hipMemsetAsync(d_ft_acc.p, 0, 3 * N * sizeof(float4), st));
         const bool tight = !(opt.exact_cull || (p.flags & AKR_PT_EXACT_CULL));
         for (int s = 0; s < p.spp; s++) {
@@ -1617,37 +1524,6 @@ struct akr_hip_ctx {
         if (p->flags & ~AKR_DENOISE_NO_DEMODULATE) throw std::runtime_error("denoise: unknown flags");
     }
 
-    // the filter on frame-ordered device buffers, enqueued on `st`
-    void denoise(const akr_denoise_params &p, int32_t width, int32_t height, const float *rad, const float *w,
-                 const float *feat, float *out, hipStream_t st) {
-        const uint32_t n = (uint32_t)((uint64_t)width * (uint64_t)height);
-        d_dn_guide.reserve(3 * (size_t)n);
-        d_dn_I[0].reserve(n);
-        d_dn_I[1].reserve(n);
-        const bool dm = !(p.flags & AKR_DENOISE_NO_DEMODULATE);
-        serialize(st);
-        timed("denoise_prep", st, [&] { launch_denoise_prep(rad, w, feat, n, dm, d_dn_guide.p, d_dn_I[0].p, st); });
-        for (int i = 0; i < p.iterations; i++) {
-            DenoiseArgs a{};
-            a.guide = d_dn_guide.p;
-            a.in = d_dn_I[i & 1].p;
-            a.out = d_dn_I[(i + 1) & 1].p;
-            a.width = width;
-            a.height = height;
-            a.step = 1 << i;
-            a.squarings = p.normal_squarings;
-            a.color_stop = p.sigma_color > 0.0f ? 1 : 0;
-            a.sigma_depth = p.sigma_depth;
-            a.sigma_albedo = p.sigma_albedo;
-            const float sc = p.sigma_color * (1.0f / (float)(1 << i));
-            a.sc2 = sc * sc;
-            timed("denoise", st, [&] { launch_denoise_atrous(a, st); });
-        }
-        timed("denoise_finish", st, [&] { launch_denoise_finish(d_dn_guide.p, d_dn_I[p.iterations & 1].p, n, dm, out, st); });
-        HIPCHK(hipGetLastError());
-        mark_done(st);
-    }
-
     // ---- the variance-guided filter
     DBuf<float4> d_dn_V[2];
 
@@ -1658,21 +1534,22 @@ struct akr_hip_ctx {
             throw std::runtime_error("denoise: sigma_variance must be > 0 and finite");
     }
 
-    // denoise() with the frame-ordered variance (vr, vg, vb, K): the same prep and finish, the guided iteration
-    void denoise_guided(const akr_denoise_guided_params &gp, int32_t width, int32_t height, const float *rad, const float *w,
-                        const float *feat, const float *var, float *out, hipStream_t st) {
-        const akr_denoise_params &p = gp.base;
+    // The filter on frame-ordered device buffers, enqueued on `st`.  var: the guided form, with the frame-ordered
+    // variance (vr, vg, vb, K) and its sigma: the same prep and finish around the guided iteration
+    void denoise(const akr_denoise_params &p, int32_t width, int32_t height, const float *rad, const float *w,
+                 const float *feat, const float *var, float sigma_variance, float *out, hipStream_t st) {
         const uint32_t n = (uint32_t)((uint64_t)width * (uint64_t)height);
         d_dn_guide.reserve(3 * (size_t)n);
         for (int k = 0; k < 2; k++) {
             d_dn_I[k].reserve(n);
-            d_dn_V[k].reserve(n);
+            if (var) d_dn_V[k].reserve(n);
         }
         const bool dm = !(p.flags & AKR_DENOISE_NO_DEMODULATE);
         serialize(st);
         timed("denoise_prep", st, [&] { launch_denoise_prep(rad, w, feat, n, dm, d_dn_guide.p, d_dn_I[0].p, st); });
-        timed("denoise_prep_variance", st,
-              [&] { launch_denoise_prep_variance(var, d_dn_guide.p, d_dn_I[0].p, n, dm, d_dn_V[0].p, st); });
+        if (var)
+            timed("denoise_prep_variance", st,
+                  [&] { launch_denoise_prep_variance(var, d_dn_guide.p, d_dn_I[0].p, n, dm, d_dn_V[0].p, st); });
         for (int i = 0; i < p.iterations; i++) {
             DenoiseGuidedArgs g{};
             DenoiseArgs &a = g.d;
@@ -1688,18 +1565,45 @@ struct akr_hip_ctx {
             a.sigma_albedo = p.sigma_albedo;
             const float sc = p.sigma_color * (1.0f / (float)(1 << i));
             a.sc2 = sc * sc;
+            if (!var) {
+                timed("denoise", st, [&] { launch_denoise_atrous(a, st); });
+                continue;
+            }
             g.vin = d_dn_V[i & 1].p;
             g.vout = d_dn_V[(i + 1) & 1].p;
-            g.sv3 = (3.0f * gp.sigma_variance) * gp.sigma_variance;
+            g.sv3 = (3.0f * sigma_variance) * sigma_variance;
             timed("denoise_guided", st, [&] { launch_denoise_atrous_guided(g, st); });
         }
         timed("denoise_finish", st, [&] { launch_denoise_finish(d_dn_guide.p, d_dn_I[p.iterations & 1].p, n, dm, out, st); });
         HIPCHK(hipGetLastError());
         mark_done(st);
     }
+
+    // The host form of both filters: the frame-ordered inputs staged on the device (`variance`: the guided
+    // form's plane, behind the others), the filter, the result back
+    void denoise_host(const akr_denoise_params &p, int32_t width, int32_t height, const float *radiance, const float *weight,
+                      const float *features, const float *variance, float sigma_variance, float *out_rgb) {
+        const size_t n = (size_t)width * (size_t)height;
+        hipStream_t st = stream;
+        serialize(st);  // the staging buffers are shared by every denoise of the context
+        d_dn_in.reserve((variance ? 20 : 16) * n);
+        d_dn_out.reserve(3 * n);
+        float *d_rad = d_dn_in.p, *d_w = d_rad + 3 * n, *d_feat = d_rad + 4 * n, *d_var = variance ? d_rad + 16 * n : nullptr;
+        HIPCHK(hipMemcpyAsync(d_rad, radiance, 3 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_w, weight, n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_feat, features, 12 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        if (variance) HIPCHK(hipMemcpyAsync(d_var, variance, 4 * n * sizeof(float), hipMemcpyHostToDevice, st));
+        denoise(p, width, height, d_rad, d_w, d_feat, d_var, sigma_variance, d_dn_out.p, st);
+        HIPCHK(hipMemcpyAsync(out_rgb, d_dn_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
+        mark_done(st);
+        HIPCHK(hipStreamSynchronize(st));
+    }
 };
 
 namespace {
+
+// the caller's stream, or the context's own
+hipStream_t stream_of(const akr_hip_ctx *ctx, void *stream) { return stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream; }
 
 template <class F>
 int guard(akr_hip_ctx *ctx, F &&f) {
@@ -1714,6 +1618,24 @@ int guard(akr_hip_ctx *ctx, F &&f) {
     } catch (...) {
         ctx->err = "unknown error";
         return -1;
+    }
+}
+
+// One call that extends or starts a session, after its argument checks (include/akr_hip.h: a refused call
+// changes nothing, a failure while rendering ends the session).  A body that throws Refused has changed
+// nothing but perhaps the session record, which is put back; after any other failure the film may be partly
+// extended, and there is no session; otherwise the session is what the body left.
+template <class F>
+void session_call(akr_hip_ctx *ctx, F &&body) {
+    const Session before = ctx->session;
+    try {
+        body();
+    } catch (const Refused &) {
+        ctx->session = before;
+        throw;
+    } catch (...) {
+        ctx->drop_session();
+        throw;
     }
 }
 
@@ -2194,7 +2116,7 @@ int akr_hip_trace_device(akr_hip_ctx *ctx, const void *d_rays, uint64_t n, void 
     return guard(ctx, [&] {
         if (n == 0) return;
         if (!d_rays || !d_hits) throw std::runtime_error("null ray or hit buffer");
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        hipStream_t st = stream_of(ctx, stream);
         ctx->trace(reinterpret_cast<const float4 *>(d_rays), n, reinterpret_cast<akr_hit *>(d_hits), any_hit, st);
     });
 }
@@ -2272,9 +2194,7 @@ int akr_hip_render_node(akr_hip_ctx *const *ctxs, int32_t n_ctx, const akr_pt_pa
             std::vector<std::vector<uint32_t>> rank;
             const std::vector<uint32_t> &pl = ctxs[k]->host_pixels();
             for (uint64_t i = 0; i < N; i++) {
-                const uint32_t px = pl[i];
-                const uint64_t p = (uint64_t)(px & 0xFFFFu) + (uint64_t)(px >> 16) * W;
-                const uint32_t r = seen[p]++;
+                const uint32_t r = seen[frame_index(pl[i], W)]++;
                 if (r >= rank.size()) rank.emplace_back();
                 rank[r].push_back((uint32_t)i);
             }
@@ -2377,13 +2297,23 @@ void merge_film(akr_hip_ctx *ctx, uint64_t N, int spp, float *radiance, float *w
     const int W = ctx->cam.width;
     const std::vector<uint32_t> &pl = ctx->host_pixels();
     for (uint64_t k = 0; k < N; k++) {
-        uint32_t px = pl[k];
-        uint64_t pix = (uint64_t)(px & 0xFFFFu) + (uint64_t)(px >> 16) * W;
+        const uint64_t pix = frame_index(pl[k], W);
         radiance[3 * pix + 0] += film[k].x;
         radiance[3 * pix + 1] += film[k].y;
         radiance[3 * pix + 2] += film[k].z;
         weight[pix] += film[k].w;
     }
+}
+
+// The same film to packed device buffers on `st`, overwriting them.  rendered: the call drew samples, whose
+// fault, without "verify", the next render reports
+void unpack_film(akr_hip_ctx *ctx, uint64_t N, int spp, float *d_radiance, float *d_weight, hipStream_t st, bool rendered,
+                 bool per_slot = false) {
+    ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)N, d_radiance, d_weight, st); });
+    HIPCHK(hipGetLastError());
+    ctx->verify_weights(st, N, spp, per_slot);
+    if (rendered) ctx->unchecked_render = !ctx->opt.verify;
+    ctx->mark_done(st);
 }
 }  // namespace
 
@@ -2393,7 +2323,7 @@ int akr_hip_render(akr_hip_ctx *ctx, const akr_pt_params *params, const akr_rect
         if (!params || !radiance || !weight) throw std::runtime_error("null argument");
         const uint64_t N = ctx->render(*params, tiles, n_tiles, ctx->stream);
         merge_film(ctx, N, params->spp, radiance, weight);
-        ctx->open_session(*params, N, params->spp, params->spp > 0);
+        open_session(ctx->session, *params, N, params->spp, params->spp > 0);
     });
 }
 
@@ -2415,14 +2345,11 @@ int akr_hip_render_features(akr_hip_ctx *ctx, const akr_feature_params *params, 
         std::vector<float> rec(12 * N);
         HIPCHK(hipMemcpyAsync(rec.data(), ctx->d_ft_acc.p, rec.size() * sizeof(float), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        const uint64_t W = (uint64_t)ctx->cam.width;
-        for (const uint4 &t : ctx->ft_tiles) {  // slot order: tiles in order, row-major inside a tile
-            const uint64_t end = &t == &ctx->ft_tiles.back() ? N : (&t)[1].w;
-            for (uint64_t i = t.w; i < end; i++) {
-                const uint64_t local = i - t.w;
-                float *dst = features + 12 * ((t.x + local % t.z) + (t.y + local / t.z) * W);
-                for (int c = 0; c < 12; c++) dst[c] += rec[12 * i + c];
-            }
+        std::vector<uint32_t> pl;
+        slot_pixels(ctx->ft_lay, pl);
+        for (uint64_t i = 0; i < N; i++) {
+            float *dst = features + 12 * frame_index(pl[i], ctx->cam.width);
+            for (int c = 0; c < 12; c++) dst[c] += rec[12 * i + c];
         }
     });
 }
@@ -2431,7 +2358,7 @@ int akr_hip_render_features_device(akr_hip_ctx *ctx, const akr_feature_params *p
                                    int32_t n_tiles, float *d_features, void *stream, uint64_t *n_pixels) {
     return guard(ctx, [&] {
         if (!params || !d_features) throw std::runtime_error("null argument");
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        hipStream_t st = stream_of(ctx, stream);
         const uint64_t N = ctx->render_features(*params, tiles, n_tiles, st);
         if (n_pixels) *n_pixels = N;
         if (N == 0) return;
@@ -2445,19 +2372,7 @@ int akr_hip_denoise(akr_hip_ctx *ctx, const akr_denoise_params *params, int32_t 
     return guard(ctx, [&] {
         if (!radiance || !weight || !features || !out_rgb) throw std::runtime_error("denoise: null argument");
         akr_hip_ctx::check_denoise(params, width, height);
-        const size_t n = (size_t)width * (size_t)height;
-        hipStream_t st = ctx->stream;
-        ctx->serialize(st);  // the staging buffers are shared by every denoise of the context
-        ctx->d_dn_in.reserve(16 * n);
-        ctx->d_dn_out.reserve(3 * n);
-        float *d_rad = ctx->d_dn_in.p, *d_w = d_rad + 3 * n, *d_feat = d_rad + 4 * n;
-        HIPCHK(hipMemcpyAsync(d_rad, radiance, 3 * n * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_w, weight, n * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_feat, features, 12 * n * sizeof(float), hipMemcpyHostToDevice, st));
-        ctx->denoise(*params, width, height, d_rad, d_w, d_feat, ctx->d_dn_out.p, st);
-        HIPCHK(hipMemcpyAsync(out_rgb, ctx->d_dn_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
-        ctx->mark_done(st);
-        HIPCHK(hipStreamSynchronize(st));
+        ctx->denoise_host(*params, width, height, radiance, weight, features, nullptr, 0.0f, out_rgb);
     });
 }
 
@@ -2467,8 +2382,8 @@ int akr_hip_denoise_device(akr_hip_ctx *ctx, const akr_denoise_params *params, i
     return guard(ctx, [&] {
         if (!d_radiance || !d_weight || !d_features || !d_out_rgb) throw std::runtime_error("denoise: null argument");
         akr_hip_ctx::check_denoise(params, width, height);
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
-        ctx->denoise(*params, width, height, d_radiance, d_weight, d_features, d_out_rgb, st);
+        hipStream_t st = stream_of(ctx, stream);
+        ctx->denoise(*params, width, height, d_radiance, d_weight, d_features, nullptr, 0.0f, d_out_rgb, st);
     });
 }
 
@@ -2478,20 +2393,7 @@ int akr_hip_denoise_guided(akr_hip_ctx *ctx, const akr_denoise_guided_params *pa
     return guard(ctx, [&] {
         if (!radiance || !weight || !features || !variance || !out_rgb) throw std::runtime_error("denoise: null argument");
         akr_hip_ctx::check_denoise_guided(params, width, height);
-        const size_t n = (size_t)width * (size_t)height;
-        hipStream_t st = ctx->stream;
-        ctx->serialize(st);  // the staging buffers are shared by every denoise of the context
-        ctx->d_dn_in.reserve(20 * n);
-        ctx->d_dn_out.reserve(3 * n);
-        float *d_rad = ctx->d_dn_in.p, *d_w = d_rad + 3 * n, *d_feat = d_rad + 4 * n, *d_var = d_rad + 16 * n;
-        HIPCHK(hipMemcpyAsync(d_rad, radiance, 3 * n * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_w, weight, n * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_feat, features, 12 * n * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_var, variance, 4 * n * sizeof(float), hipMemcpyHostToDevice, st));
-        ctx->denoise_guided(*params, width, height, d_rad, d_w, d_feat, d_var, ctx->d_dn_out.p, st);
-        HIPCHK(hipMemcpyAsync(out_rgb, ctx->d_dn_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
-        ctx->mark_done(st);
-        HIPCHK(hipStreamSynchronize(st));
+        ctx->denoise_host(params->base, width, height, radiance, weight, features, variance, params->sigma_variance, out_rgb);
     });
 }
 
@@ -2502,8 +2404,8 @@ int akr_hip_denoise_guided_device(akr_hip_ctx *ctx, const akr_denoise_guided_par
         if (!d_radiance || !d_weight || !d_features || !d_variance || !d_out_rgb)
             throw std::runtime_error("denoise: null argument");
         akr_hip_ctx::check_denoise_guided(params, width, height);
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
-        ctx->denoise_guided(*params, width, height, d_radiance, d_weight, d_features, d_variance, d_out_rgb, st);
+        hipStream_t st = stream_of(ctx, stream);
+        ctx->denoise(params->base, width, height, d_radiance, d_weight, d_features, d_variance, params->sigma_variance, d_out_rgb, st);
     });
 }
 
@@ -2523,7 +2425,7 @@ int akr_hip_render_variance(akr_hip_ctx *ctx, float *variance) {
         const int W = ctx->cam.width;
         const std::vector<uint32_t> &pl = ctx->host_pixels();
         for (uint64_t k = 0; k < N; k++) {
-            const uint64_t pix = (uint64_t)(pl[k] & 0xFFFFu) + (uint64_t)(pl[k] >> 16) * W;
+            const uint64_t pix = frame_index(pl[k], W);
             for (int c = 0; c < 4; c++) variance[4 * pix + c] += rec[4 * k + c];
         }
     });
@@ -2532,7 +2434,7 @@ int akr_hip_render_variance(akr_hip_ctx *ctx, float *variance) {
 int akr_hip_render_variance_device(akr_hip_ctx *ctx, float *d_variance, void *stream, uint64_t *n_pixels) {
     return guard(ctx, [&] {
         if (!d_variance) throw std::runtime_error("null argument");
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+        hipStream_t st = stream_of(ctx, stream);
         const uint64_t N = ctx->variance_resolve(d_variance, st);
         if (n_pixels) *n_pixels = N;
         ctx->mark_done(st);
@@ -2543,109 +2445,73 @@ int akr_hip_render_device(akr_hip_ctx *ctx, const akr_pt_params *params, const a
                           float *d_radiance, float *d_weight, void *stream, uint64_t *n_pixels) {
     return guard(ctx, [&] {
         if (!params || !d_radiance || !d_weight) throw std::runtime_error("null argument");
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
-        uint64_t N = ctx->render(*params, tiles, n_tiles, st);
+        hipStream_t st = stream_of(ctx, stream);
+        const uint64_t N = ctx->render(*params, tiles, n_tiles, st);
         if (n_pixels) *n_pixels = N;
-        ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)N, d_radiance, d_weight, st); });
-        HIPCHK(hipGetLastError());
-        ctx->verify_weights(st, N, params->spp);
-        ctx->unchecked_render = !ctx->opt.verify;
-        ctx->mark_done(st);
-        ctx->open_session(*params, N, params->spp, params->spp > 0);
+        unpack_film(ctx, N, params->spp, d_radiance, d_weight, st, true);
+        open_session(ctx->session, *params, N, params->spp, params->spp > 0);
     });
 }
 
 namespace {
-// The session's parameters with `spp` more samples for every slot, checked
-akr_pt_params continue_params(akr_hip_ctx *ctx, int32_t spp) {
-    const akr_hip_ctx::Session &s = ctx->require_session();
+// The checks of a continue of `spp` samples for every slot
+void check_continue(const akr_hip_ctx *ctx, int32_t spp, const void *radiance, const void *weight) {
+    if (!radiance || !weight) throw std::runtime_error("null argument");
+    const Session &s = ctx->require_session();
     if (spp < 0) throw std::runtime_error("spp must be >= 0");
-    if ((int64_t)s.spp_done + spp > akr_hip_ctx::kSessionSppCap) akr_hip_ctx::throw_cap(s.spp_done, spp);
-    return ctx->session_params(spp);
+    check_cap(s.spp_done, spp);
 }
 
-// After a continue of spp > 0 samples for every slot on `st`: the per-slot counts of a non-uniform
-// session, and the copy `s` of the session that the caller stores once the whole call has succeeded
-void advance_session(akr_hip_ctx *ctx, akr_hip_ctx::Session &s, int32_t spp, hipStream_t st) {
+// spp more samples for every slot on `st`, and the per-slot counts of a non-uniform session with them
+void continue_all(akr_hip_ctx *ctx, int32_t spp, hipStream_t st) {
+    Session &s = ctx->session;
+    if (spp == 0) return;
+    ctx->render(session_params(s, spp), nullptr, 0, st, true);
     if (!s.uniform) launch_count_add(ctx->d_count.p, nullptr, (uint32_t)s.n, (uint32_t)spp, st);
-    s.spp_done += spp;
-    s.spp_min += spp;
-    s.seeded = true;
-    s.ad.on = false;
+    advance_all(s, spp);
 }
 }  // namespace
 
 int akr_hip_render_continue(akr_hip_ctx *ctx, int32_t spp, float *radiance, float *weight) {
     return guard(ctx, [&] {
-        if (!radiance || !weight) throw std::runtime_error("null argument");
-        const akr_pt_params p = continue_params(ctx, spp);
-        akr_hip_ctx::Session s = ctx->session;
-        try {
-            if (spp > 0) {
-                ctx->render(p, nullptr, 0, ctx->stream, true);
-                advance_session(ctx, s, spp, ctx->stream);
-            }
+        check_continue(ctx, spp, radiance, weight);
+        session_call(ctx, [&] {
+            continue_all(ctx, spp, ctx->stream);
+            const Session &s = ctx->session;
             merge_film(ctx, s.n, s.spp_done, radiance, weight, !s.uniform);
-        } catch (...) {  // a segment that fails leaves no session: its film may be partly extended
-            ctx->drop_session();
-            throw;
-        }
-        ctx->session = s;
+        });
     });
 }
 
 int akr_hip_render_continue_device(akr_hip_ctx *ctx, int32_t spp, float *d_radiance, float *d_weight, void *stream,
                                    uint64_t *n_pixels) {
     return guard(ctx, [&] {
-        if (!d_radiance || !d_weight) throw std::runtime_error("null argument");
-        const akr_pt_params p = continue_params(ctx, spp);
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
-        akr_hip_ctx::Session s = ctx->session;
-        const uint64_t N = s.n;
-        try {
-            if (spp > 0) {
-                ctx->render(p, nullptr, 0, st, true);
-                advance_session(ctx, s, spp, st);
-            } else {
-                ctx->serialize(st);
-            }
-            if (n_pixels) *n_pixels = N;
-            ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)N, d_radiance, d_weight, st); });
-            HIPCHK(hipGetLastError());
-            ctx->verify_weights(st, N, s.spp_done, !s.uniform);
-            if (spp > 0) ctx->unchecked_render = !ctx->opt.verify;
-            ctx->mark_done(st);
-        } catch (...) {
-            ctx->drop_session();
-            throw;
-        }
-        ctx->session = s;
+        check_continue(ctx, spp, d_radiance, d_weight);
+        hipStream_t st = stream_of(ctx, stream);
+        session_call(ctx, [&] {
+            if (spp == 0) ctx->serialize(st);
+            continue_all(ctx, spp, st);
+            const Session &s = ctx->session;
+            if (n_pixels) *n_pixels = s.n;
+            unpack_film(ctx, s.n, s.spp_done, d_radiance, d_weight, st, spp > 0, !s.uniform);
+        });
     });
 }
 
 namespace {
-// the session's totals to the caller: host form (added into full-frame buffers) or device form (packed)
-void session_film_host(akr_hip_ctx *ctx, float *radiance, float *weight) {
-    const akr_hip_ctx::Session &s = ctx->session;
-    merge_film(ctx, s.n, s.spp_done, radiance, weight, !s.uniform);
-}
-void session_film_device(akr_hip_ctx *ctx, float *d_radiance, float *d_weight, hipStream_t st, bool rendered) {
-    const akr_hip_ctx::Session &s = ctx->session;
-    ctx->timed("unpack", st, [&] { launch_unpack(ctx->d_film.p, (uint32_t)s.n, d_radiance, d_weight, st); });
-    HIPCHK(hipGetLastError());
-    ctx->verify_weights(st, s.n, s.spp_done, !s.uniform);
-    if (rendered) ctx->unchecked_render = !ctx->opt.verify;
-    ctx->mark_done(st);
-}
-
-// spp more samples for the slots whose byte of the device mask is set
-void continue_masked(akr_hip_ctx *ctx, int32_t spp, const uint8_t *d_mask, uint64_t n, hipStream_t st) {
-    const akr_hip_ctx::Session &s = ctx->require_session();
+// The checks of a masked continue, host and device form
+void check_masked(const akr_hip_ctx *ctx, int32_t spp, const uint8_t *mask, uint64_t n, const void *radiance, const void *weight) {
+    if (!radiance || !weight) throw std::runtime_error("null argument");
+    const Session &s = ctx->require_session();
     if (spp < 0) throw std::runtime_error("spp must be >= 0");
     if (n != s.n)
         throw std::runtime_error("masked continue: the mask has " + std::to_string(n) + " bytes, the session has " +
                                  std::to_string(s.n) + " slots");
-    if (n && !d_mask) throw std::runtime_error("null argument");
+    if (n && !mask) throw std::runtime_error("null argument");
+}
+
+// spp more samples for the slots whose byte of the device mask is set
+void continue_masked(akr_hip_ctx *ctx, int32_t spp, const uint8_t *d_mask, uint64_t n, hipStream_t st) {
     ctx->serialize(st);
     if (spp == 0 || n == 0) return;
     ctx->session.ad.on = false;
@@ -2657,61 +2523,37 @@ void continue_masked(akr_hip_ctx *ctx, int32_t spp, const uint8_t *d_mask, uint6
 int akr_hip_render_continue_masked(akr_hip_ctx *ctx, int32_t spp, const uint8_t *mask, uint64_t n, float *radiance,
                                    float *weight) {
     return guard(ctx, [&] {
-        if (!radiance || !weight) throw std::runtime_error("null argument");
-        const akr_hip_ctx::Session &s = ctx->require_session();
-        if (spp < 0) throw std::runtime_error("spp must be >= 0");
-        if (n != s.n)
-            throw std::runtime_error("masked continue: the mask has " + std::to_string(n) + " bytes, the session has " +
-                                     std::to_string(s.n) + " slots");
-        if (n && !mask) throw std::runtime_error("null argument");
+        check_masked(ctx, spp, mask, n, radiance, weight);
         hipStream_t st = ctx->stream;
-        const akr_hip_ctx::Session before = ctx->session;
-        bool rendering = false;
-        try {
-            if (n) {
-                ctx->serialize(st);
-                ctx->d_mask.upload(mask, n, st);
-            }
-            rendering = true;
-            continue_masked(ctx, spp, ctx->d_mask.p, n, st);
-            session_film_host(ctx, radiance, weight);
-        } catch (const akr_hip_ctx::Refused &) {  // the cap: nothing changed
-            ctx->session = before;
-            throw;
-        } catch (...) {  // a pass that fails while rendering ends the session
-            if (rendering) ctx->drop_session();
-            throw;
+        if (n) {  // not yet rendering: a failed upload keeps the session
+            ctx->serialize(st);
+            ctx->d_mask.upload(mask, n, st);
         }
+        session_call(ctx, [&] {
+            continue_masked(ctx, spp, ctx->d_mask.p, n, st);
+            const Session &s = ctx->session;
+            merge_film(ctx, s.n, s.spp_done, radiance, weight, !s.uniform);
+        });
     });
 }
 
 int akr_hip_render_continue_masked_device(akr_hip_ctx *ctx, int32_t spp, const uint8_t *d_mask, uint64_t n,
                                           float *d_radiance, float *d_weight, void *stream, uint64_t *n_pixels) {
     return guard(ctx, [&] {
-        if (!d_radiance || !d_weight) throw std::runtime_error("null argument");
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
-        const akr_hip_ctx::Session before = ctx->require_session();
-        if (spp < 0) throw std::runtime_error("spp must be >= 0");
-        if (n != before.n)
-            throw std::runtime_error("masked continue: the mask has " + std::to_string(n) + " bytes, the session has " +
-                                     std::to_string(before.n) + " slots");
-        try {
+        check_masked(ctx, spp, d_mask, n, d_radiance, d_weight);
+        hipStream_t st = stream_of(ctx, stream);
+        session_call(ctx, [&] {
             continue_masked(ctx, spp, d_mask, n, st);
-            if (n_pixels) *n_pixels = before.n;
-            session_film_device(ctx, d_radiance, d_weight, st, spp > 0);
-        } catch (const akr_hip_ctx::Refused &) {  // the cap: nothing changed
-            ctx->session = before;
-            throw;
-        } catch (...) {
-            ctx->drop_session();
-            throw;
-        }
+            const Session &s = ctx->session;
+            if (n_pixels) *n_pixels = s.n;
+            unpack_film(ctx, s.n, s.spp_done, d_radiance, d_weight, st, spp > 0, !s.uniform);
+        });
     });
 }
 
 int akr_hip_render_state_spp_range(akr_hip_ctx *ctx, int32_t *spp_min, int32_t *spp_max) {
     return guard(ctx, [&] {
-        const akr_hip_ctx::Session &s = ctx->require_session();
+        const Session &s = ctx->require_session();
         if (spp_min) *spp_min = s.uniform ? s.spp_done : s.spp_min;
         if (spp_max) *spp_max = s.spp_done;
     });
@@ -2724,7 +2566,7 @@ void check_adaptive(const akr_pt_params *params, const akr_adaptive_params *ap) 
     if (ap->min_spp < 1) throw std::runtime_error("adaptive render: min_spp must be >= 1");
     if (ap->pass_spp < 0) throw std::runtime_error("adaptive render: pass_spp must be >= 0");
     if (!(ap->threshold >= 0.0f)) throw std::runtime_error("adaptive render: threshold must be >= 0 and not NaN");
-    if (params->spp > akr_hip_ctx::kSessionSppCap) throw std::runtime_error("adaptive render: the cap exceeds 2^24 samples");
+    if (params->spp > kSessionSppCap) throw std::runtime_error("adaptive render: the cap exceeds 2^24 samples");
 }
 
 // The adaptive loop in two pieces, both on `st`.  adaptive_begin: min_spp for every
@@ -2736,23 +2578,10 @@ uint64_t adaptive_begin(akr_hip_ctx *ctx, const akr_pt_params &params, const akr
     akr_pt_params p0 = params;
     p0.spp = std::min(cap, ap.min_spp);
     const uint64_t N = ctx->render(p0, tiles, n_tiles, st);
-    ctx->open_session(p0, N, p0.spp, p0.spp > 0);
-    const uint64_t n_strips = (N + 63) / 64;
-    akr_hip_ctx::Session::Adaptive &ad = ctx->session.ad;
-    ad = akr_hip_ctx::Session::Adaptive{};
-    ad.on = true;
-    ad.cap = cap;
-    ad.pass_spp = ap.pass_spp;
-    ad.threshold = ap.threshold;
-    ad.total = p0.spp;
-    ad.m = (uint32_t)N;
-    akr_adaptive_info &out = ad.info;
-    out.passes = 1;
-    out.spp_min = out.spp_max = p0.spp;
-    out.samples = N * (uint64_t)p0.spp;
-    out.strips = n_strips;
-    ad.more = cap > ap.min_spp && N > 0;
-    if (ad.more) {
+    open_session(ctx->session, p0, N, p0.spp, p0.spp > 0);
+    adaptive_open(ctx->session, cap, ap);
+    const uint64_t n_strips = ctx->session.ad.info.strips;
+    if (ctx->session.ad.more) {
         // the first pass is complete on the host before its film is copied (as merge_film waits before
         // its read-back); then the snapshot, every strip active, every slot masked
         ctx->host_join();
@@ -2766,44 +2595,23 @@ uint64_t adaptive_begin(akr_hip_ctx *ctx, const akr_pt_params &params, const akr
         HIPCHK(hipMemsetAsync(ctx->d_mask.p, 1, N, st));
         HIPCHK(hipMemsetAsync(ctx->d_strip_active.p, 1, n_strips, st));
         HIPCHK(hipMemsetAsync(ctx->d_strip_err.p, 0, n_strips * sizeof(float), st));
-        ctx->session.n_strips = n_strips;
     }
     return N;
 }
 
 void adaptive_step(akr_hip_ctx *ctx, hipStream_t st) {
-    akr_hip_ctx::Session &s = ctx->session;
-    akr_hip_ctx::Session::Adaptive &ad = s.ad;
-    if (!ctx->require_session().ad.on)
-        throw std::runtime_error("adaptive step: the session is not an adaptive render in progress "
-                                 "(start one with akr_hip_adaptive_begin; a continue with samples ends it)");
+    Session &s = ctx->session;
+    const Session::Adaptive &ad = s.ad;
     if (!ad.more) return;
     const uint32_t N = (uint32_t)s.n;
-    akr_adaptive_info &out = ad.info;
-    // every active strip holds ad.total samples; the pass is clipped at the cap
-    const int64_t want = ad.pass_spp > 0 ? (int64_t)ad.total + ad.pass_spp : 2 * (int64_t)ad.total;
-    const int32_t step = (int32_t)(std::min<int64_t>(want, ad.cap) - ad.total);
+    const int32_t step = adaptive_pass_spp(ad);
     ctx->render_subset(step, ad.m, st, false);
-    ad.total += step;
-    out.passes++;
-    out.samples += (uint64_t)ad.m * (uint64_t)step;
     ctx->timed("adaptive_test", st, [&] {
         launch_adaptive_test(ctx->d_film.p, ctx->d_prev.p, N, ad.threshold, ctx->d_strip_err.p, ctx->d_strip_active.p,
                              ctx->d_mask.p, st);
     });
     HIPCHK(hipGetLastError());
-    const uint32_t before = ad.m;
-    ad.m = ctx->compact_mask(ctx->d_mask.p, N, st);  // the pass's one host read: the active count
-    if (!ad.some_stopped) {  // no strip had stopped before this test: the smallest count follows the total
-        out.spp_min = ad.total;
-        if (ad.m < before) ad.some_stopped = true;
-    }
-    out.spp_max = ad.total;
-    s.spp_done = out.spp_max;
-    s.spp_min = out.spp_min;
-    ad.more = ad.m > 0 && ad.total < ad.cap;
-    // strips are 64 slots, but for a short last one
-    out.strips_at_cap = ad.total >= ad.cap ? ((uint64_t)ad.m + 63) / 64 : 0;
+    adaptive_advance(s, step, ctx->compact_mask(ctx->d_mask.p, N, st));  // the pass's one host read: the active count
 }
 
 uint64_t render_adaptive(akr_hip_ctx *ctx, const akr_pt_params &params, const akr_adaptive_params &ap,
@@ -2820,15 +2628,12 @@ int akr_hip_adaptive_begin(akr_hip_ctx *ctx, const akr_pt_params *params, const 
     return guard(ctx, [&] {
         check_adaptive(params, ap);
         hipStream_t st = ctx->stream;
-        try {
+        session_call(ctx, [&] {
             adaptive_begin(ctx, *params, *ap, tiles, n_tiles, st);
-            const akr_hip_ctx::Session &s = ctx->session;
+            const Session &s = ctx->session;
             ctx->verify_weights(st, s.n, s.spp_done);
             ctx->mark_done(st);
-        } catch (...) {
-            ctx->drop_session();
-            throw;
-        }
+        });
         if (info) *info = ctx->session.ad.info;
         if (more) *more = ctx->session.ad.more ? 1 : 0;
     });
@@ -2836,18 +2641,15 @@ int akr_hip_adaptive_begin(akr_hip_ctx *ctx, const akr_pt_params *params, const 
 
 int akr_hip_adaptive_step(akr_hip_ctx *ctx, akr_adaptive_info *info, int32_t *more) {
     return guard(ctx, [&] {
-        if (!ctx->require_session().ad.on) adaptive_step(ctx, ctx->stream);  // throws the message
+        require_adaptive(ctx->session);
         hipStream_t st = ctx->stream;
-        try {
+        session_call(ctx, [&] {
             ctx->serialize(st);
             adaptive_step(ctx, st);
-            const akr_hip_ctx::Session &s = ctx->session;
+            const Session &s = ctx->session;
             ctx->verify_weights(st, s.n, s.spp_done, !s.uniform);
             ctx->mark_done(st);
-        } catch (...) {
-            ctx->drop_session();
-            throw;
-        }
+        });
         if (info) *info = ctx->session.ad.info;
         if (more) *more = ctx->session.ad.more ? 1 : 0;
     });
@@ -2859,13 +2661,11 @@ int akr_hip_render_adaptive(akr_hip_ctx *ctx, const akr_pt_params *params, const
     return guard(ctx, [&] {
         check_adaptive(params, ap);
         if (!radiance || !weight) throw std::runtime_error("null argument");
-        try {
+        session_call(ctx, [&] {
             render_adaptive(ctx, *params, *ap, tiles, n_tiles, ctx->stream, info);
-            session_film_host(ctx, radiance, weight);
-        } catch (...) {
-            ctx->drop_session();
-            throw;
-        }
+            const Session &s = ctx->session;
+            merge_film(ctx, s.n, s.spp_done, radiance, weight, !s.uniform);
+        });
     });
 }
 
@@ -2875,21 +2675,19 @@ int akr_hip_render_adaptive_device(akr_hip_ctx *ctx, const akr_pt_params *params
     return guard(ctx, [&] {
         check_adaptive(params, ap);
         if (!d_radiance || !d_weight) throw std::runtime_error("null argument");
-        hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
-        try {
+        hipStream_t st = stream_of(ctx, stream);
+        session_call(ctx, [&] {
             const uint64_t N = render_adaptive(ctx, *params, *ap, tiles, n_tiles, st, info);
             if (n_pixels) *n_pixels = N;
-            session_film_device(ctx, d_radiance, d_weight, st, true);
-        } catch (...) {
-            ctx->drop_session();
-            throw;
-        }
+            const Session &s = ctx->session;
+            unpack_film(ctx, s.n, s.spp_done, d_radiance, d_weight, st, true, !s.uniform);
+        });
     });
 }
 
 int akr_hip_adaptive_error(akr_hip_ctx *ctx, float *strip_error, uint8_t *strip_active, uint64_t n_strips) {
     return guard(ctx, [&] {
-        const akr_hip_ctx::Session &s = ctx->require_session();
+        const Session &s = ctx->require_session();
         if (s.n_strips == 0) throw std::runtime_error("adaptive error: the session ran no convergence test");
         if (n_strips != s.n_strips)
             throw std::runtime_error("adaptive error: n_strips is " + std::to_string(n_strips) + ", the session has " +
@@ -2907,7 +2705,7 @@ int akr_hip_adaptive_error(akr_hip_ctx *ctx, float *strip_error, uint8_t *strip_
 int akr_hip_render_state_info(akr_hip_ctx *ctx, akr_render_state_info *info) {
     return guard(ctx, [&] {
         if (!info) throw std::runtime_error("null argument");
-        const akr_hip_ctx::Session &s = ctx->require_session();
+        const Session &s = ctx->require_session();
         *info = akr_render_state_info{};
         info->n_pixels = s.n;
         info->spp_done = s.spp_done;
@@ -2916,13 +2714,13 @@ int akr_hip_render_state_info(akr_hip_ctx *ctx, akr_render_state_info *info) {
         info->flags = s.flags;
         info->width = ctx->cam.width;
         info->height = ctx->cam.height;
-        info->n_tiles = (int32_t)ctx->h_tiles.size();
+        info->n_tiles = (int32_t)ctx->lay.tiles.size();
     });
 }
 
 int akr_hip_render_state_export(akr_hip_ctx *ctx, uint32_t *sampler, float *film, uint64_t n) {
     return guard(ctx, [&] {
-        const akr_hip_ctx::Session &s = ctx->require_session();
+        const Session &s = ctx->require_session();
         if (n != s.n) throw std::runtime_error("render state export: n is " + std::to_string(n) + ", the session has " +
                                                std::to_string(s.n) + " slots");
         if (n == 0) return;
@@ -2935,7 +2733,7 @@ int akr_hip_render_state_export(akr_hip_ctx *ctx, uint32_t *sampler, float *film
         } else {  // no sample drawn yet: the slots' start states
             const int W = ctx->cam.width;
             const std::vector<uint32_t> &pl = ctx->host_pixels();
-            for (uint64_t k = 0; k < n; k++) sampler[k] = (uint32_t)((int)(pl[k] & 0xFFFFu) + (int)(pl[k] >> 16) * W);
+            for (uint64_t k = 0; k < n; k++) sampler[k] = (uint32_t)frame_index(pl[k], W);
         }
         HIPCHK(hipMemcpyAsync(film, ctx->d_film.p, n * sizeof(float4), hipMemcpyDeviceToHost, st));
         ctx->mark_done(st);
@@ -2949,17 +2747,12 @@ int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, c
         if (!params) throw std::runtime_error("null argument");
         if (params->spp < 0 || params->max_depth < 0) throw std::runtime_error("spp and max_depth must be >= 0");
         if (params->max_depth > 1000) throw std::runtime_error("max_depth too large");
-        if (params->spp > akr_hip_ctx::kSessionSppCap) throw std::runtime_error("render state import: spp exceeds 2^24");
+        if (params->spp > kSessionSppCap) throw std::runtime_error("render state import: spp exceeds 2^24");
         if (n && (!sampler || !film)) throw std::runtime_error("null argument");
         if (!ctx->cam_set) throw std::runtime_error("camera not set (call akr_hip_set_camera)");
         if (n_tiles < 0 || (n_tiles > 0 && !tiles)) throw std::runtime_error("invalid tile list");
         // validated before anything of the context changes: a refused import keeps the current session
-        uint64_t want = 0;
-        for (int k = 0; k < n_tiles; k++) {
-            const int x0 = std::max(0, tiles[k].x0), y0 = std::max(0, tiles[k].y0);
-            const int x1 = std::min(ctx->cam.width, tiles[k].x1), y1 = std::min(ctx->cam.height, tiles[k].y1);
-            if (x1 > x0 && y1 > y0) want += (uint64_t)(x1 - x0) * (uint64_t)(y1 - y0);
-        }
+        const uint64_t want = layout_tiles(tiles, n_tiles, ctx->cam.width, ctx->cam.height, "render call").n;
         if (n != want) throw std::runtime_error("render state import: n is " + std::to_string(n) + ", the tile list has " +
                                                 std::to_string(want) + " pixels");
         for (uint64_t k = 0; k < n; k++)
@@ -2981,7 +2774,7 @@ int akr_hip_render_state_import(akr_hip_ctx *ctx, const akr_pt_params *params, c
         HIPCHK(hipStreamSynchronize(st));  // the caller's arrays are free again
         ctx->probe_ok = false;
         ctx->probe_n = 0;
-        ctx->open_session(*params, N, params->spp, true);
+        open_session(ctx->session, *params, N, params->spp, true);
     });
 }
 

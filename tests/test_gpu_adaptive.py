@@ -180,6 +180,16 @@ def test_masked_continue_device_form(hip_ctx_factory):
             with pytest.raises(capi.AkrError, match="the mask has"):
                 ctx.render_continue_masked_device(1, d_mask.p.value, n - 1, d_rad.p.value, d_w.p.value)
             assert ctx.render_state_spp_range() == (3, 8)
+            # a null mask is refused like the host form's: the session stays, and goes on
+            with pytest.raises(capi.AkrError, match="null argument"):
+                ctx.render_continue_masked_device(1, 0, n, d_rad.p.value, d_w.p.value)
+            assert ctx.render_state_spp_range() == (3, 8)
+            assert ctx.render_continue_masked_device(2, d_mask.p.value, n, d_rad.p.value, d_w.p.value) == n
+            ctx.synchronize()
+            film = _expected(frame, np.where(mask != 0, 10, 3), ys, xs, W, H)[0]
+            assert np.array_equal(d_w.get(np.float32), film[:, 3])
+            assert np.array_equal(d_rad.get(np.float32).reshape(-1, 3), film[:, :3])
+            assert ctx.render_state_spp_range() == (3, 10)
         finally:
             ctx.synchronize()
             for d in (d_mask, d_rad, d_w):
