@@ -143,6 +143,7 @@ PT_EXACT_CULL = 1
 BUILDER_SAH, BUILDER_LBVH, BUILDER_SBVH = 0, 1, 2
 COLLAPSE_SAH, COLLAPSE_BALANCED = 0, 1   # akr_build_params::wide_collapse
 MAT_DIFFUSE, MAT_GLOSSY, MAT_EMISSIVE, MAT_MIX = 0, 1, 2, 3
+MAT_MIRROR, MAT_GLASS = 4, 5   # DESIGN.md section 3.19; a Glass holds its ior's texture index in `roughness`
 PROBE_SEED, PROBE_RAYS = 1, 2
 FORM_NAMES = {-1: None, 0: "wavefront", 2: "k_path", 3: "k_path_defer", 4: "k_path_spec"}
 SHADING_NAMES = {-1: None, 0: "general", 1: "simple"}   # AKR_SHADING_* (akr_hip_render_shading)

@@ -61,7 +61,18 @@ class MixMaterial:              # material.h:241-248 (first = material_A, second
     second: "MaterialT"
 
 
-MaterialT = Union[DiffuseMaterial, GlossyMaterial, EmissiveMaterial, MixMaterial]
+@dataclass(eq=False)
+class MirrorMaterial:           # not the reference's: perfect specular reflection
+    color: Texture              # reflectance
+
+
+@dataclass(eq=False)
+class GlassMaterial:            # not the reference's: a smooth dielectric, Fresnel reflection and refraction
+    color: Texture              # tint of both lobes
+    ior: float = 1.5            # index of refraction against the outside's 1: a constant in [1, 8]
+
+
+MaterialT = Union[DiffuseMaterial, GlossyMaterial, EmissiveMaterial, MixMaterial, MirrorMaterial, GlassMaterial]
 
 
 @dataclass(eq=False)
@@ -271,6 +282,7 @@ def compile_scene(scene: Scene) -> CompiledScene:
     textures: List[capi.Texture] = []
     images: List[np.ndarray] = []
     materials: List[capi.Material] = []
+    ior_tex: List[ConstantTexture] = []
 
     def tex_index(t: Texture) -> int:
         if id(t) in tex_ids:
@@ -304,6 +316,18 @@ def compile_scene(scene: Scene) -> CompiledScene:
             cm.type, cm.fraction = capi.MAT_MIX, tex_index(m.fraction)
             cm.first = mat_index(m.first)
             cm.second = mat_index(m.second)
+        elif isinstance(m, MirrorMaterial):
+            cm.type, cm.color = capi.MAT_MIRROR, tex_index(m.color)
+        elif isinstance(m, GlassMaterial):
+            if isinstance(m.ior, (ConstantTexture, ImageTexture)) or isinstance(m.ior, bool):
+                raise TypeError("GlassMaterial: ior is a number (an image-textured ior is not supported)")
+            ior = float(F32(m.ior))
+            if not (math.isfinite(ior) and 1.0 <= ior <= 8.0):
+                raise ValueError(f"GlassMaterial: ior {m.ior!r} is not a finite number in [1, 8]")
+            # the ior rides in `roughness` as a constant texture of its own (akr_hip.h)
+            cm.type, cm.color = capi.MAT_GLASS, tex_index(m.color)
+            ior_tex.append(ConstantTexture([ior] * 3))   # kept alive: tex_index remembers textures by id()
+            cm.roughness = tex_index(ior_tex[-1])
         else:
             raise TypeError(f"unsupported material {type(m).__name__}")
         materials[idx] = cm
@@ -633,6 +657,17 @@ class SdlParser:
             return EmissiveMaterial(self._texture(f.get("color", 0.0)), False)
         if t == "MixMaterial":
             return MixMaterial(self._texture(f.get("fraction", 0.5)), f["first"], f["second"])
+        if t == "MirrorMaterial":
+            return MirrorMaterial(self._texture(f.get("color", 1.0)))
+        if t == "GlassMaterial":
+            ior = f.get("ior", 1.5)
+            if isinstance(ior, (str, ImageTexture)):
+                self._err("GlassMaterial: ior is a number; an image-textured ior is not supported")
+            if isinstance(ior, bool) or not isinstance(ior, (int, float)):
+                self._err("GlassMaterial: ior is a number")
+            if not (math.isfinite(ior) and 1.0 <= float(F32(ior)) <= 8.0):
+                self._err(f"GlassMaterial: ior {ior} is not a finite number in [1, 8]")
+            return GlassMaterial(self._texture(f.get("color", 1.0)), float(F32(ior)))
         if t == "AkariMesh":
             mesh = load_mesh(self.path.parent / f["path"])
             mesh.materials = list(f.get("materials", []))

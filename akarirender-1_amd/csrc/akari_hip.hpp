@@ -54,6 +54,18 @@ struct SceneDesc {
     akr_camera camera{};
 };
 
+// Mirror and Glass, which the reference lacks: the records SceneDesc::materials takes.
+// `color` names a texture (reflectance / tint); a Glass's `ior` names a constant texture whose x is the index
+// of refraction, carried in akr_material::roughness.
+inline akr_material mirror_material(int32_t color) {
+    akr_material m{AKR_MAT_MIRROR, color, -1, -1, -1, -1, 0};
+    return m;
+}
+inline akr_material glass_material(int32_t color, int32_t ior) {
+    akr_material m{AKR_MAT_GLASS, color, ior, -1, -1, -1, 0};
+    return m;
+}
+
 class HipAccelerator {
   public:
     explicit HipAccelerator(int device = 0) {

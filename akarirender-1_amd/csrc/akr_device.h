@@ -237,6 +237,26 @@ struct ShadeEnvMisArgs {
     MisDev m;
 };
 
+// Mirror and Glass: what k_shade_spec / k_shade_env_spec read and write beside k_shade's
+// arguments.  A path carries one bit, via_delta: its last scattering vertex sampled a delta lobe.  The bit
+// travels with the path state (ping-ponged with the state queues, as MisDev's carried record is); the MIS
+// builds hold it in that record instead (p_b < 0) and take ShadeMisArgs / ShadeEnvMisArgs as they are.
+// E is §3.18's: what an emitter or the environment adds to a path that reaches it via_delta at depth > 0.
+struct SpecDev {
+    const uint32_t *flag_in;            // per queue entry: the ray that found this hit left a delta lobe
+    uint32_t *flag_out;                 // the same for the extension rays this launch appends
+    float4 *E;                          // per slot: the terminal term (zeroed per pass), added to L by k_splat_mis
+};
+struct ShadeSpecArgs {
+    ShadeArgs s;
+    SpecDev d;
+};
+struct ShadeEnvSpecArgs {
+    ShadeArgs s;
+    EnvDev env;
+    SpecDev d;
+};
+
 // The unit entry points (akr_hip_environment_sample / _eval): n inputs (2 floats u, or 3 floats of a
 // world direction) -> world direction (sample only), texel rgb with the scale applied, solid-angle pdf
 struct EnvUnitArgs {

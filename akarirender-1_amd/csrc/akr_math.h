@@ -129,8 +129,11 @@ __device__ __forceinline__ float ggx_g1(float alpha, V3 v, V3 m) {
 }
 
 // BSDF closure kinds (material.h:139-155)
-enum : int { CL_NONE = 0, CL_DIFFUSE = 1, CL_GLOSSY = 2 };
-struct Closure { int kind; V3 R; float alpha; };
+// CL_MIRROR / CL_GLASS are delta lobes the reference lacks: closure_eval is 0 for them
+// (its last return), closure_sample_delta draws them, and no caller asks closure_pdf about them
+enum : int { CL_NONE = 0, CL_DIFFUSE = 1, CL_GLOSSY = 2, CL_MIRROR = 3, CL_GLASS = 4 };
+struct Closure { int kind; V3 R; float alpha; };  // alpha: Glossy's roughness squared, Glass's ior
+__device__ __forceinline__ bool closure_is_delta(const Closure &c) { return c.kind >= CL_MIRROR; }
 
 // DiffuseBSDF::evaluate (material.h:72-77) / MicrofacetReflection::evaluate (:99-121)
 __device__ __forceinline__ V3 closure_eval(const Closure &c, V3 wo, V3 wi) {
@@ -185,6 +188,7 @@ __device__ __forceinline__ V3 closure_sample(const Closure &c, V2 u, V3 wo, V3 &
 // DiffuseBSDF::evaluate_pdf / MicrofacetReflection::evaluate_pdf (material.h), which the reference's path
 // tracer never calls: the pdf closure_sample draws wi with, without choice_pdf
 __device__ __forceinline__ float closure_pdf(const Closure &c, V3 wo, V3 wi) {
+    if (closure_is_delta(c)) return 0.0f;  // no density over directions
     if (!same_hemisphere(wo, wi)) return 0.0f;
     if (c.kind == CL_DIFFUSE) return fabsf(wi.y) * kInvPi;
     V3 wh = add(wo, wi);
@@ -192,6 +196,36 @@ __device__ __forceinline__ float closure_pdf(const Closure &c, V3 wo, V3 wi) {
     wh = normalize(wh);
     if (wh.y < 0) wh = neg(wh);
     return ggx_d(c.alpha, wh) * fabsf(wh.y) / (4.0f * fabsf(dot(wo, wh)));
+}
+
+// Mirror and Glass (tests/golden/specular_restate.py is the definition).  wo in the shading
+// frame, y the normal.  Select-shaped: the Fresnel terms and both candidate directions are computed by every
+// lane, and reflect / refract / total internal reflection differ only in what is selected; a Mirror is the
+// reflection taken with weight 1.  The choice reads u.y: under a Mix u.x is the selection's own number.
+// Only add, subtract, multiply, divide, sqrt, abs and compare: each is the restatement's IEEE operation.
+__device__ __forceinline__ V3 closure_sample_delta(const Closure &c, V2 u, V3 wo, V3 &wi, float &pdf) {
+    const float co = fabsf(wo.y);
+    wi = v3(-wo.x, wo.y, -wo.z);
+    if (co == 0.0f) {
+        pdf = 0;
+        return v3(0, 0, 0);
+    }
+    const bool glass = c.kind == CL_GLASS;
+    const bool entering = wo.y > 0.0f;
+    const float ior = glass ? c.alpha : 1.0f;
+    const float ei = entering ? 1.0f : ior, et = entering ? ior : 1.0f;
+    const float r = ei / et;
+    const float s2 = (r * r) * rmax(0.0f, 1.0f - co * co);
+    const bool tir = s2 >= 1.0f;
+    const float ct = sqrtf(1.0f - s2);  // NaN under total internal reflection, where nothing reads it
+    const float rp = (et * co - ei * ct) / (et * co + ei * ct);
+    const float rs = (ei * co - et * ct) / (ei * co + et * ct);
+    const float F = tir ? 1.0f : (rp * rp + rs * rs) * 0.5f;
+    const bool refl = !glass || u.y < F;
+    const float w = !glass ? 1.0f : (refl ? F : 1.0f - F);
+    if (!refl) wi = v3(-r * wo.x, entering ? -ct : ct, -r * wo.z);  // not renormalised
+    pdf = w;
+    return divs(muls(c.R, w), fabsf(wi.y));
 }
 
 // The power heuristic w(a, b) = 1 / (1 + (b / a)^2), a the pdf of the strategy that drew the direction

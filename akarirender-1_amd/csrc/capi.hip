@@ -336,6 +336,21 @@ struct akr_hip_ctx {
             tri_sel_dirty = false;
         }
     }
+    // Mirror and Glass, for renders of a scene that holds one: the via_delta flag
+    // queues (ping-ponged with the state queues; the MIS builds keep the bit in d_carry instead) and d_E above.
+    // spec_on is commit_scene()'s has_specular as the render call read it: the scene decides, not the session,
+    // so render() asks at every call, and a continue of a session whose buffers stand reserves nothing.
+    DBuf<uint32_t> d_spec_flag[2];
+    bool has_specular = false;
+    bool spec_on = false;
+    void spec_begin(uint64_t N) {
+        spec_on = has_specular;
+        if (!spec_on || N == 0) return;
+        for (int k = 0; k < 2; k++) {
+            d_E[k].reserve(N);
+            if (!mis_on) d_spec_flag[k].reserve(N);
+        }
+    }
     std::vector<uint32_t> h_pixel;
     bool h_pixel_ok = false;
     DBuf<uint32_t> d_pixel, d_seed, d_slot0, d_slot1, d_counts;
@@ -504,9 +519,23 @@ struct akr_hip_ctx {
             if (x.type == AKR_MAT_DIFFUSE || x.type == AKR_MAT_EMISSIVE) ok = tex_ok(x.color);
             else if (x.type == AKR_MAT_GLOSSY) ok = tex_ok(x.color) && tex_ok(x.roughness);
             else if (x.type == AKR_MAT_MIX) ok = tex_ok(x.fraction) && mat_ok(x.first) && mat_ok(x.second);
+            else if (x.type == AKR_MAT_MIRROR) ok = tex_ok(x.color);
+            else if (x.type == AKR_MAT_GLASS) ok = tex_ok(x.color) && tex_ok(x.roughness);
             else ok = false;
             if (!ok) throw std::runtime_error("material " + std::to_string(m) + " has an invalid type or reference");
+            if (x.type == AKR_MAT_GLASS) {  // the index of refraction: `roughness` reused
+                const akr_texture &t = texs[x.roughness];
+                if (t.type != AKR_TEX_CONSTANT)
+                    throw std::runtime_error("material " + std::to_string(m) +
+                                             ": a Glass's index of refraction must be a constant texture, not an image");
+                const float ior = t.value[0];
+                if (!std::isfinite(ior) || ior < 1.0f || ior > 8.0f)
+                    throw std::runtime_error("material " + std::to_string(m) +
+                                             ": a Glass's index of refraction must be finite and lie in [1, 8]");
+            }
         }
+        has_specular = false;
+        for (auto &m : mats) has_specular = has_specular || m.type == AKR_MAT_MIRROR || m.type == AKR_MAT_GLASS;
         // shading the persistent path kernels run well inline: constant Diffuse / Emissive only
         simple_shading = true;
         for (auto &m : mats) simple_shading = simple_shading && (m.type == AKR_MAT_DIFFUSE || m.type == AKR_MAT_EMISSIVE);
@@ -1090,6 +1119,7 @@ struct akr_hip_ctx {
         const uint64_t N = cont ? resume_pixels(n_count_words, st) : setup_pixels(tiles, n_tiles, n_count_words, st);
         if (!cont) variance_begin(N, st);  // zeroed on st beside the render; the update follows the join below
         if (!cont) mis_begin(N, st);       // a continue keeps the session's value
+        spec_begin(N);                     // the committed scene's, at every call
         if (N == 0) return 0;
         if (subset && (!cont || n_subset == 0 || n_subset > N)) throw std::runtime_error("render: invalid slot subset");
         const uint64_t M = subset ? n_subset : N;  // the slots this pass fetches
@@ -1121,7 +1151,8 @@ struct akr_hip_ctx {
         // and render_path() runs k_path's environment build
         // and so does option "mis": its kernels are the wavefront's
         const bool env_wavefront = env_on() && !opt.env_path;
-        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_wavefront && !mis_on) {
+        // and so does a scene that holds a Mirror or a Glass: k_shade_spec and its forms
+        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_wavefront && !mis_on && !spec_on) {
             if (p.spp > 0) render_path(pass);
             last_passes = 1;
         } else {
@@ -1271,8 +1302,12 @@ struct akr_hip_ctx {
         const SceneDev sd = scene_dev();
         if (p.spp > 0) last_form = AKR_FORM_WAVEFRONT;
         if (p.spp > 0) last_shading = AKR_SHADING_GENERAL;
-        const int nb = p.max_depth == 0 ? 1 : p.max_depth;  // the trace at depth == max_depth can
-                                                             // add nothing: skipped
+        const int nb_plain = p.max_depth == 0 ? 1 : p.max_depth;  // the trace at depth == max_depth can
+                                                                   // add nothing: skipped
+        // with a Mirror or a Glass it can: a ray that left a delta lobe at the last scattering vertex may still
+        // meet an emitter or the sky.  Only such rays are queued for it (shade_hit_tab, SPEC), DESIGN.md §3.19
+        const int nb = spec_on && p.max_depth > 0 ? p.max_depth + 1 : nb_plain;
+        const bool with_E = mis_on || spec_on;  // the terminal accumulator and k_splat_mis
         int64_t g = 0;  // bounce index over all passes: shadow queues alternate by its parity
         const uint32_t *worder = nullptr;  // the cost order of the camera rays (option wave_order)
         if (opt.wave_order && opt.path_order != 0 && !subset && p.spp >= order_min_spp(opt, N) && N >= 2) {
@@ -1292,7 +1327,7 @@ struct akr_hip_ctx {
             // L[ps] and the counter set were last used by pass s - 2, whose splat ends its side-stream work
             if (s >= 2) HIPCHK(hipStreamWaitEvent(ms, ev_splat[ps], 0));
             HIPCHK(hipMemsetAsync(cnt, 0, n_count_words * sizeof(uint32_t), ms));
-            if (mis_on) HIPCHK(hipMemsetAsync(d_E[ps].p, 0, N * sizeof(float4), ms));  // like L[ps]: free since pass s - 2
+            if (with_E) HIPCHK(hipMemsetAsync(d_E[ps].p, 0, N * sizeof(float4), ms));  // like L[ps]: free since pass s - 2
             RaygenArgs rg = raygen_args((uint32_t)M, L, qcount(0), s == 0 && !resume);
             rg.probe = probe_p;
             rg.order = subset ? subset : worder;
@@ -1325,7 +1360,7 @@ struct akr_hip_ctx {
                 sh.L = L;  // written at depth 0 only, before any shadow trace of the pass
                 sh.depth = b;
                 sh.max_depth = p.max_depth;
-                sh.last = b == nb - 1;
+                sh.last = b >= nb_plain - 1;
                 sh.probe = probe_p;
                 // MIS: the terminal term goes to E[ps], never to L, which the side stream's shadow trace of the
                 // bounce before may be adding to; one queue entry per slot per launch, so E needs no atomic
@@ -1334,7 +1369,20 @@ struct akr_hip_ctx {
                 md.carry_out = odd ? d_carry[0].p : d_carry[1].p;
                 md.tri_sel = (decltype(md.tri_sel))d_tri_sel.p;  // device code sees it as a global pointer
                 md.E = d_E[ps].p;
-                if (mis_on && env_on())
+                // a Mirror or a Glass in the scene: the specular forms; the via_delta bit rides in md's carried
+                // record under MIS and in a flag queue of its own otherwise
+                SpecDev sv{};
+                sv.flag_in = odd ? d_spec_flag[1].p : d_spec_flag[0].p;
+                sv.flag_out = odd ? d_spec_flag[0].p : d_spec_flag[1].p;
+                sv.E = d_E[ps].p;
+                if (spec_on && mis_on && env_on())
+                    timed("shade", ms, [&] { launch_shade_env_spec_mis(ShadeEnvMisArgs{sh, env, md}, (uint32_t)M, ms); });
+                else if (spec_on && mis_on)
+                    timed("shade", ms, [&] { launch_shade_spec_mis(ShadeMisArgs{sh, md}, (uint32_t)M, ms); });
+                else if (spec_on && env_on())
+                    timed("shade", ms, [&] { launch_shade_env_spec(ShadeEnvSpecArgs{sh, env, sv}, (uint32_t)M, ms); });
+                else if (spec_on) timed("shade", ms, [&] { launch_shade_spec(ShadeSpecArgs{sh, sv}, (uint32_t)M, ms); });
+                else if (mis_on && env_on())
                     timed("shade", ms, [&] { launch_shade_env_mis(ShadeEnvMisArgs{sh, env, md}, (uint32_t)M, ms); });
                 else if (mis_on) timed("shade", ms, [&] { launch_shade_mis(ShadeMisArgs{sh, md}, (uint32_t)M, ms); });
                 else if (env_on()) timed("shade", ms, [&] { launch_shade_env(ShadeEnvArgs{sh, env}, (uint32_t)M, ms); });
@@ -1367,7 +1415,7 @@ struct akr_hip_ctx {
             sp.n = (uint32_t)M;
             sp.ray_clamp = p.ray_clamp;
             sp.order = subset;
-            if (mis_on) timed("splat", side, [&] { launch_splat_mis(SplatMisArgs{sp, d_E[ps].p}, (uint32_t)M, side); });
+            if (with_E) timed("splat", side, [&] { launch_splat_mis(SplatMisArgs{sp, d_E[ps].p}, (uint32_t)M, side); });
             else timed("splat", side, [&] { launch_splat(sp, (uint32_t)M, side); });
             HIPCHK(hipEventRecord(ev_splat[ps], side));
         }

@@ -21,6 +21,12 @@ void launch_shade_env(const ShadeEnvArgs &a, uint32_t max_items, hipStream_t st)
 void launch_shade_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st);
 void launch_shade_env_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st);
 void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st);
+// for scenes that hold a Mirror or a Glass: the four shade kernels' specular forms; the film
+// is splatted by launch_splat_mis over SpecDev::E or MisDev::E
+void launch_shade_spec(const ShadeSpecArgs &a, uint32_t max_items, hipStream_t st);
+void launch_shade_env_spec(const ShadeEnvSpecArgs &a, uint32_t max_items, hipStream_t st);
+void launch_shade_spec_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st);
+void launch_shade_env_spec_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st);
 void launch_env_unit(bool sample, const EnvUnitArgs &a, hipStream_t st);
 void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, uint32_t *gate, hipStream_t st);
 void launch_store_word(const uint32_t *src, uint32_t *dst, hipStream_t st);

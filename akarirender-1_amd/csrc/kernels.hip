@@ -1209,11 +1209,16 @@ __device__ __forceinline__ V3 chan_rgb(const SceneDev &s, const C &c, int32_t im
     else return mat_rgb(s, c, img, tc);
 }
 
-template <class Tab, bool ENV = false, bool MIS = false, bool SIMPLE = false>
+// SPEC: the build for scenes that hold a Mirror or a Glass.  via_delta: the ray that found
+// this hit left a delta lobe, so an emitter counts at full weight as it does for the camera ray (o.emit; the
+// caller keeps the term out of L at depth > 0).  *delta: the closure sampled here was one; its extension ray is
+// traced even from the last scattering vertex, since only such a ray can still meet an emitter.
+template <class Tab, bool ENV = false, bool MIS = false, bool SIMPLE = false, bool SPEC = false>
 __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab, uint32_t gid, float u, float v, V3 wo,
                                               V3 beta, uint32_t &seed, int depth, int max_depth, bool last, Bounce &o,
                                               unsigned long long *t_load = nullptr, const EnvDev *env = nullptr,
-                                              const MisHit *mh = nullptr, MisOut *mo = nullptr) {
+                                              const MisHit *mh = nullptr, MisOut *mo = nullptr, bool via_delta = false,
+                                              bool *delta = nullptr) {
     o.emit = o.ext = o.sh = false;
     unsigned long long t0 = 0;  // counting builds (t_load): ticks until the shading record is in
     if (t_load) t0 = wall_clock64();
@@ -1238,7 +1243,7 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
     }
     auto mat = tab.mat(mid);
     if (mat->type == AKR_MAT_EMISSIVE) {
-        if (depth == 0) {
+        if (depth == 0 || (SPEC && via_delta)) {
             const bool face_front = dot(neg(wo), ng) < 0.0f;
             if (mat->double_sided || face_front) {
                 o.emit = true;
@@ -1296,17 +1301,30 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
         float r = mat_x(s, mat->rough, mat->rough_img, tc);
         r *= r;
         cl.alpha = r;
+    } else if (SPEC && mat->type == AKR_MAT_MIRROR) {
+        cl.kind = CL_MIRROR;
+        cl.R = mat_rgb(s, mat->color, mat->color_img, tc);
+    } else if (SPEC && mat->type == AKR_MAT_GLASS) {
+        cl.kind = CL_GLASS;
+        cl.R = mat_rgb(s, mat->color, mat->color_img, tc);
+        cl.alpha = mat->rough;  // the ior: a constant, commit_scene() refuses an image
     }
+    [[maybe_unused]] bool is_delta = false;
+    if constexpr (SPEC) is_delta = closure_is_delta(cl);
+    if constexpr (SPEC && MIS) pair = pair && !is_delta;  // a delta vertex is never paired
     const Frame frame = make_frame(ns);
     const V2 bu = lcg_next2(seed);  // BSDFSampleContext(sampler.next2d(), wo)
     if (cl.kind == CL_NONE) return;
     V3 wi_l;
     float pdf = 0.0f;
-    const V3 f = closure_sample(cl, bu, to_local(frame, wo), wi_l, pdf);
+    V3 f;
+    if (SPEC && is_delta) f = closure_sample_delta(cl, bu, to_local(frame, wo), wi_l, pdf);
+    else f = closure_sample(cl, bu, to_local(frame, wo), wi_l, pdf);
     const V3 wi = to_world(frame, wi_l);
     [[maybe_unused]] const float p_b = pdf;  // MIS carries closure_sample's value, not a re-evaluation from (wo, wi)
     pdf *= choice_pdf;
     if (pdf == 0.0f) return;
+    if constexpr (SPEC) *delta = is_delta;
     if constexpr (MIS) {
         if (pair && p_b > 0.0f) {  // direct lighting's convention: ns, no choice_pdf
             const V3 T = divs(mul(beta, muls(f, fabsf(dot(ns, wi)))), p_b);
@@ -1387,7 +1405,7 @@ __device__ __forceinline__ void shade_hit_tab(const SceneDev &s, const Tab &tab,
             }
         }
     }
-    if (!last) {
+    if (!last || (SPEC && is_delta)) {
         o.ext = true;
         o.nb = mul(beta, ev_beta);
         o.e0 = make_float4(p.x, p.y, p.z, kEps / cng);
@@ -1414,8 +1432,12 @@ __device__ __forceinline__ void shade_hit(const SceneDev &s, uint32_t gid, float
 #define AKR_SHADE_BLOCK 256
 #endif
 constexpr int kShadeBlock = AKR_SHADE_BLOCK;  // threads per shade workgroup (one queue atomic each)
-template <bool ENV, bool MIS = false>
-__device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *env, const MisDev *m = nullptr) {
+// SPEC: the path's via_delta bit travels with the queue entry, in SpecDev's flag queue or,
+// in the MIS builds, as the carried record's p_b < 0 (a delta vertex carries no pair); what an emitter or
+// the environment adds to a path that reaches it via_delta at depth > 0 is the terminal term E, as §3.18's
+template <bool ENV, bool MIS = false, bool SPEC = false>
+__device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *env, const MisDev *m = nullptr,
+                                            const SpecDev *sd = nullptr) {
     const uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x;
     const uint32_t n = *a.count_in;
     if (blockIdx.x * kShadeBlock >= n) return;  // whole workgroup past the queue (uniform: before any barrier)
@@ -1425,6 +1447,7 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
     [[maybe_unused]] MisOut mo;
     mo.term = false;
     mo.carry = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    [[maybe_unused]] bool via = false, delta = false;
     if (i < n) {
         slot = a.slot_in[i];
         const float4 stv = a.state_in[i];
@@ -1436,9 +1459,24 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
             mh.carry = a.depth > 0 ? m->carry_in[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             mh.tri_sel = m->tri_sel;
         }
+        if constexpr (SPEC) {
+            if (a.depth > 0) {
+                if constexpr (MIS) via = mh.carry.w < 0.0f;
+                else via = sd->flag_in[i] != 0u;
+            }
+        }
         if (gid != kNoHit) {  // miss -> on_miss (no-op), the path ends
             const float4 rdv = a.ray_in[2 * (size_t)i + 1];
-            if constexpr (MIS) {
+            if constexpr (SPEC) {
+                if constexpr (MIS) {
+                    const float4 rov = a.ray_in[2 * (size_t)i];
+                    mh.ro = v3(rov.x, rov.y, rov.z);
+                }
+                shade_hit_tab<GlobalTab, ENV, MIS, false, true>(a.sc, global_tab(a.sc), gid, hv.y, hv.z,
+                                                                neg(v3(rdv.x, rdv.y, rdv.z)), V3{stv.x, stv.y, stv.z}, seed,
+                                                                a.depth, a.max_depth, a.last != 0, bo, nullptr, env,
+                                                                MIS ? &mh : nullptr, MIS ? &mo : nullptr, via, &delta);
+            } else if constexpr (MIS) {
                 const float4 rov = a.ray_in[2 * (size_t)i];
                 mh.ro = v3(rov.x, rov.y, rov.z);
                 shade_hit_tab<GlobalTab, ENV, true>(a.sc, global_tab(a.sc), gid, hv.y, hv.z, neg(v3(rdv.x, rdv.y, rdv.z)),
@@ -1451,7 +1489,10 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
             else
                 shade_hit(a.sc, gid, hv.y, hv.z, neg(v3(rdv.x, rdv.y, rdv.z)), V3{stv.x, stv.y, stv.z}, seed, a.depth,
                           a.max_depth, a.last != 0, bo);
-            if (bo.emit) {
+            if (SPEC && bo.emit && a.depth > 0) {  // reached via_delta: the terminal term, never L (§3.18 "Why E exists")
+                mo.term = true;
+                mo.E = bo.e;
+            } else if (bo.emit) {
                 float4 l = a.L[slot];
                 l.x += bo.e.x;
                 l.y += bo.e.y;
@@ -1470,6 +1511,13 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
                 l.y += e.y;
                 l.z += e.z;
                 a.L[slot] = l;
+            } else if (SPEC && via) {  // a ray that left a delta lobe sees the map as the camera ray does
+                const float4 rdv = a.ray_in[2 * (size_t)i + 1];
+                int ti, tj;
+                float len;
+                env_encode(env->n, env_to_map(*env, v3(rdv.x, rdv.y, rdv.z)), ti, tj, len);
+                mo.term = true;
+                mo.E = mul(V3{stv.x, stv.y, stv.z}, env_lookup(*env, ti, tj));
             } else if constexpr (MIS) {
                 if (mh.carry.w > 0.0f) {  // the BSDF sample reached the environment: its share of direct lighting
                     const float4 rdv = a.ray_in[2 * (size_t)i + 1];
@@ -1485,8 +1533,11 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
                 }
             }
         }
-        if constexpr (MIS)
+        if constexpr (MIS) {
             if (mo.term) m->E[slot] = make_float4(mo.E.x, mo.E.y, mo.E.z, 0.0f);  // the path ends here: once per pass
+        } else if constexpr (SPEC) {
+            if (mo.term) sd->E[slot] = make_float4(mo.E.x, mo.E.y, mo.E.z, 0.0f);
+        }
         // the path does not reach another traced bounce: persist its sampler stream for the next
         // sample (the stream continues across spp, cpu/integrator.cpp:124-134)
         if (!bo.ext) a.seed[slot] = seed;
@@ -1504,7 +1555,9 @@ __device__ __forceinline__ void shade_queue(const ShadeArgs &a, const EnvDev *en
         a.ray_out[2 * (size_t)pos + 1] = bo.e1;
         a.state_out[pos] = make_float4(bo.nb.x, bo.nb.y, bo.nb.z, bitsf(seed));
         a.slot_out[pos] = slot;
-        if constexpr (MIS) m->carry_out[pos] = mo.carry;
+        if constexpr (MIS && SPEC) m->carry_out[pos] = delta ? make_float4(0.0f, 0.0f, 0.0f, -1.0f) : mo.carry;
+        else if constexpr (MIS) m->carry_out[pos] = mo.carry;
+        else if constexpr (SPEC) sd->flag_out[pos] = delta ? 1u : 0u;
     }
     if (bo.sh) {  // the shadow trace adds the colour to L[colour.w] when unoccluded
         a.shadow_ray[2 * (size_t)spos] = bo.s0;
@@ -3740,7 +3793,8 @@ __global__ __launch_bounds__(kBlock) void k_feature_shade(FeatureArgs a) {
                 mat = s.mats + mat->first;
             }
         }
-        if (mat->type == AKR_MAT_DIFFUSE || mat->type == AKR_MAT_GLOSSY || mat->type == AKR_MAT_EMISSIVE)
+        if (mat->type == AKR_MAT_DIFFUSE || mat->type == AKR_MAT_GLOSSY || mat->type == AKR_MAT_EMISSIVE ||
+            mat->type == AKR_MAT_MIRROR || mat->type == AKR_MAT_GLASS)
             alb = mat_rgb(s, mat->color, mat->color_img, tc);
     }
     float4 r0 = a.acc[3 * (size_t)i], r1 = a.acc[3 * (size_t)i + 1], r2 = a.acc[3 * (size_t)i + 2];
@@ -3758,6 +3812,23 @@ __global__ __launch_bounds__(kBlock) void k_feature_shade(FeatureArgs a) {
     a.acc[3 * (size_t)i] = r0;
     a.acc[3 * (size_t)i + 1] = r1;
     a.acc[3 * (size_t)i + 2] = r2;
+}
+
+// ---------------------------------------------------------------------------- specular shading
+// k_shade and its three forms for scenes that hold a Mirror or a Glass.  They stand after
+// every other kernel of this file, so the kernels before them keep their place in the code object (the
+// template kernels' instantiations are emitted after them, in the order they had).
+__global__ __launch_bounds__(kShadeBlock) void k_shade_spec(ShadeSpecArgs a) {
+    shade_queue<false, false, true>(a.s, nullptr, nullptr, &a.d);
+}
+__global__ __launch_bounds__(kShadeBlock) void k_shade_env_spec(ShadeEnvSpecArgs a) {
+    shade_queue<true, false, true>(a.s, &a.env, nullptr, &a.d);
+}
+__global__ __launch_bounds__(kShadeBlock) void k_shade_spec_mis(ShadeMisArgs a) {
+    shade_queue<false, true, true>(a.s, nullptr, &a.m);
+}
+__global__ __launch_bounds__(kShadeBlock) void k_shade_env_spec_mis(ShadeEnvMisArgs a) {
+    shade_queue<true, true, true>(a.s, &a.env, &a.m);
 }
 
 // ------------------------------------------------------------------------------------ launch
@@ -3838,6 +3909,24 @@ void launch_shade_env_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStrea
     if (max_items == 0) return;
     const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
     hipLaunchKernelGGL(k_shade_env_mis, grid, dim3(kShadeBlock), 0, st, a);
+}
+template <class K, class A>
+static void launch_shade_kernel(K kernel, const A &a, uint32_t max_items, hipStream_t st) {
+    if (max_items == 0) return;
+    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
+    hipLaunchKernelGGL(kernel, grid, dim3(kShadeBlock), 0, st, a);
+}
+void launch_shade_spec(const ShadeSpecArgs &a, uint32_t max_items, hipStream_t st) {
+    launch_shade_kernel(k_shade_spec, a, max_items, st);
+}
+void launch_shade_env_spec(const ShadeEnvSpecArgs &a, uint32_t max_items, hipStream_t st) {
+    launch_shade_kernel(k_shade_env_spec, a, max_items, st);
+}
+void launch_shade_spec_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st) {
+    launch_shade_kernel(k_shade_spec_mis, a, max_items, st);
+}
+void launch_shade_env_spec_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st) {
+    launch_shade_kernel(k_shade_env_spec_mis, a, max_items, st);
 }
 void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st) {
     if (max_items == 0) return;

@@ -36,9 +36,12 @@ inline void resolve_material(const akr_material &x, const Tex *texs, size_t n_te
     d.first = x.first;
     d.second = x.second;
     d.color_img = d.rough_img = d.frac_img = -1;
-    if (x.type == AKR_MAT_DIFFUSE || x.type == AKR_MAT_EMISSIVE || x.type == AKR_MAT_GLOSSY)
+    if (x.type == AKR_MAT_DIFFUSE || x.type == AKR_MAT_EMISSIVE || x.type == AKR_MAT_GLOSSY ||
+        x.type == AKR_MAT_MIRROR || x.type == AKR_MAT_GLASS)
         resolve_channel(texs, n_texs, x.color, d.color, 3, d.color_img);
-    if (x.type == AKR_MAT_GLOSSY) resolve_channel(texs, n_texs, x.roughness, &d.rough, 1, d.rough_img);
+    // Glass: `rough` holds the index of refraction (a constant: commit_scene() refuses an image)
+    if (x.type == AKR_MAT_GLOSSY || x.type == AKR_MAT_GLASS)
+        resolve_channel(texs, n_texs, x.roughness, &d.rough, 1, d.rough_img);
     if (x.type == AKR_MAT_MIX) resolve_channel(texs, n_texs, x.fraction, &d.frac, 1, d.frac_img);
 }
 

@@ -79,11 +79,15 @@ typedef struct akr_texture {
     int32_t _pad[3];
 } akr_texture;
 
-enum { AKR_MAT_DIFFUSE = 0, AKR_MAT_GLOSSY = 1, AKR_MAT_EMISSIVE = 2, AKR_MAT_MIX = 3 };
+/* Mirror and Glass are perfectly specular: a scene that holds one renders in the
+ * wavefront form.  A light triangle must still be Emissive. */
+enum { AKR_MAT_DIFFUSE = 0, AKR_MAT_GLOSSY = 1, AKR_MAT_EMISSIVE = 2, AKR_MAT_MIX = 3, AKR_MAT_MIRROR = 4,
+       AKR_MAT_GLASS = 5 };
 typedef struct akr_material {
     int32_t type;
-    int32_t color;      /* texture index: Diffuse/Glossy/Emissive colour */
-    int32_t roughness;  /* texture index: Glossy roughness (x channel, squared -> alpha) */
+    int32_t color;      /* texture index: Diffuse/Glossy/Emissive colour, Mirror reflectance, Glass tint */
+    int32_t roughness;  /* texture index: Glossy roughness (x channel, squared -> alpha); Glass reuses it for
+                           the index of refraction (x channel of a constant texture, finite, in [1, 8]) */
     int32_t fraction;   /* texture index: Mix fraction (x channel) */
     int32_t first;      /* material index: Mix material_A */
     int32_t second;     /* material index: Mix material_B */
