@@ -30,6 +30,10 @@ batch, so the render has to run in passes; --aov then also writes PREFIX.varianc
        ... --env FILE --env-path
 With an environment, --env-path sets library option "env_path" on every context: the persistent path
 kernel renders the scene where the render form rule takes it.  The image is the same.
+       ... --env FILE --env-path --env-forms
+--env-forms (with --env-path) sets library option "env_forms" on every context as well: the form rule then
+chooses among k_path, k_path_defer and k_path_spec as it does without an environment, which
+is what a rank's share of a --gpus N render takes.  The image is the same.
 """
 from __future__ import annotations
 
@@ -104,10 +108,11 @@ class FilmPost:
 
 
 def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[FilmPost] = None,
-                 env_path: bool = False, **build_kw) -> Tuple[np.ndarray, np.ndarray]:
+                 env_path: bool = False, env_forms: bool = False, **build_kw) -> Tuple[np.ndarray, np.ndarray]:
     """Render `sc` with its integrator node; returns the film (radiance [H,W,3], weight [H,W]).  With
     `post`, the features and the filter run on the first device after the film is gathered.
-    env_path: option "env_path" on every context (a choice of form under an environment, same bits)."""
+    env_path: option "env_path" on every context (a choice of form under an environment, same bits);
+    env_forms: option "env_forms" as well (set only when asked for)."""
     cs = scene.compile_scene(sc)
     w, h = (int(v) for v in sc.camera.resolution)
     it = sc.integrator
@@ -118,6 +123,8 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[
             if getattr(it, "mis", False):   # a session switch, read when the render starts
                 c.set_option("mis", 1)
             c.set_option("env_path", 1 if env_path else 0)
+            if env_forms:
+                c.set_option("env_forms", 1)
         if isinstance(it, scene.AOIntegrator):
             if len(ctxs) != 1:
                 raise ValueError("the AO integrator renders on one device")
@@ -142,7 +149,7 @@ def render_scene(sc: scene.Scene, devices: Sequence[int] = (0,), post: Optional[
 
 def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optional[int] = None,
                              on_pass=None, time_budget: Optional[float] = None, checkpoint=None, resume=None,
-                             post: Optional[FilmPost] = None, env_path: bool = False,
+                             post: Optional[FilmPost] = None, env_path: bool = False, env_forms: bool = False,
                              **build_kw) -> Tuple[np.ndarray, np.ndarray, int]:
     """Render a Path scene in passes on one device; returns (radiance, weight, spp_done).
 
@@ -168,6 +175,8 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
         scene.upload_scene(ctx, cs, **build_kw)
         ctx.set_option("mis", 1 if it.mis else 0)   # before the restore: a session reads it when it starts
         ctx.set_option("env_path", 1 if env_path else 0)   # read at every render and continue; not in the checkpoint
+        if env_forms:   # the same: a choice of form, the same bits
+            ctx.set_option("env_forms", 1)
         if post is not None:
             post.start(ctx)   # before the restore: an imported film is the tracker's first batch
             post.bind(tiles, w, h)
@@ -192,7 +201,7 @@ def render_scene_progressive(sc: scene.Scene, device: int = 0, pass_spp: Optiona
 
 def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, min_spp: int = 16,
                           pass_spp: Optional[int] = None, on_pass=None, time_budget: Optional[float] = None,
-                          post: Optional[FilmPost] = None, env_path: bool = False, **build_kw):
+                          post: Optional[FilmPost] = None, env_path: bool = False, env_forms: bool = False, **build_kw):
     """Render a Path scene adaptively on one device; returns (radiance, weight, info).  The integrator's
     spp is the cap; weight holds each pixel's sample count (progressive.render_adaptive)."""
     it = sc.integrator
@@ -205,6 +214,8 @@ def render_scene_adaptive(sc: scene.Scene, threshold: float, device: int = 0, mi
         scene.upload_scene(ctx, cs, **build_kw)
         ctx.set_option("mis", 1 if it.mis else 0)
         ctx.set_option("env_path", 1 if env_path else 0)
+        if env_forms:
+            ctx.set_option("env_forms", 1)
         tiles = _tiles(sc, it.tile_size)
         each = on_pass
         if post is not None:
@@ -282,6 +293,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--env-path", action="store_true",
                     help="with an environment: let the persistent path kernel render the scene where the render "
                          "form rule takes it (library option env_path); the image is the same, bit for bit")
+    ap.add_argument("--env-forms", action="store_true",
+                    help="with --env-path: let the render form rule choose among k_path, k_path_defer and k_path_spec "
+                         "as it does without an environment (library option env_forms); the image is the same")
     ap.add_argument("--env-res", type=int, default=None, metavar="N",
                     help="resolution of the octahedral map made from a lat-long image, 1..2048")
     args = ap.parse_args(argv)
@@ -289,6 +303,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--env-res needs 1..2048")
     if args.env_scale is not None and not args.env_scale >= 0:
         ap.error("--env-scale needs a number >= 0")
+    if args.env_forms and not args.env_path:
+        ap.error("--env-forms needs --env-path")
     if args.denoise_iters is not None:  # refused before the scene is read
         if not args.denoise:
             ap.error("--denoise-iters needs --denoise")
@@ -379,7 +395,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             per_pass = args.preview or args.time_budget is not None
             rad, wt, info = render_scene_adaptive(sc, args.adaptive, 0, min_spp=args.min_spp, pass_spp=args.pass_spp,
                                                   on_pass=show_adaptive if per_pass else None,
-                                                  time_budget=args.time_budget, post=post, env_path=args.env_path)
+                                                  time_budget=args.time_budget, post=post, env_path=args.env_path, env_forms=args.env_forms)
         except ValueError as e:
             ap.error(str(e))
         done = f"{info['spp_min']}..{info['spp_max']} ({info['samples']} samples in {info['passes']} passes)"
@@ -394,11 +410,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         try:
             rad, wt, done = render_scene_progressive(sc, 0, pass_spp=args.pass_spp, on_pass=show,
                                                      time_budget=args.time_budget, checkpoint=args.checkpoint,
-                                                     resume=args.resume, post=post, env_path=args.env_path)
+                                                     resume=args.resume, post=post, env_path=args.env_path, env_forms=args.env_forms)
         except progressive.CheckpointError as e:
             ap.error(str(e))
     else:
-        rad, wt = render_scene(sc, devices=list(range(args.gpus)), post=post, env_path=args.env_path)
+        rad, wt = render_scene(sc, devices=list(range(args.gpus)), post=post, env_path=args.env_path, env_forms=args.env_forms)
         done = sc.integrator.spp
     write_out(rad, wt)
     if args.aov is not None:

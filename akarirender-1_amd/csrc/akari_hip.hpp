@@ -395,6 +395,11 @@ class HipPathTracer {
     void set_env_path(const HipAccelerator &scene, bool on = true) const {
         check(scene.handle(), akr_hip_set_option(scene.handle(), "env_path", on ? 1 : 0), "set_env_path");
     }
+    // ... and let the form rule choose among k_path, k_path_defer and k_path_spec as it does without an
+    // environment (option "env_forms"): acts with set_env_path(true) only; the same bits.
+    void set_env_forms(const HipAccelerator &scene, bool on = true) const {
+        check(scene.handle(), akr_hip_set_option(scene.handle(), "env_forms", on ? 1 : 0), "set_env_forms");
+    }
     void render_variance(const HipAccelerator &scene, const Film &film, std::vector<float> &variance) const {
         variance.assign(4 * (size_t)film.width * film.height, 0.0f);
         check(scene.handle(), akr_hip_render_variance(scene.handle(), variance.data()), "render_variance");

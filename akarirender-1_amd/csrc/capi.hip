@@ -383,6 +383,17 @@ struct akr_hip_ctx {
         if (!g) g = std::min<uint32_t>((uint32_t)(n_cu * path_env_blocks_per_cu(tab, leaf_one, simple)), ovf_threads / kTraceBlock);
         return g;
     }
+    // the same of k_path_defer's and k_path_spec's environment builds [kind][tab][simple] (launch_path_env_form),
+    // queried when option env_forms first renders with one; PATH_PLAIN is env_grid()
+    uint32_t path_env_form_grid[3][2][2] = {};
+    uint32_t env_form_grid(int kind, bool tab, bool leaf_one, bool simple) {
+        if (kind == PATH_PLAIN) return env_grid(tab, leaf_one, simple);
+        uint32_t &g = path_env_form_grid[kind][tab][simple];
+        if (!g)
+            g = std::min<uint32_t>((uint32_t)(n_cu * path_env_form_blocks_per_cu(kind, tab, leaf_one, simple)),
+                                   ovf_threads / kTraceBlock);
+        return g;
+    }
     // the render form rule is plan_path() in path_plan.h; its knobs are in `opt`
     // the last render's form inputs (akr_hip_render_form_inputs): pixels per lane x 1000, the pilot's
     // rays and their summed steps
@@ -1228,11 +1239,15 @@ struct akr_hip_ctx {
         in.subset = r.subset != nullptr;
         in.n_tris = n_tris();
         in.bvh_dev_bytes = bvh_dev_bytes;
-        // an environment (option env_path): only k_path has a build for it
+        // an environment (option env_path): k_path's build for it alone, unless option
+        // env_forms lets the rule decide as it does without one; each kind's environment kernel then carries
+        // the plan out
         const bool envp = env_on();
-        in.plain_only = envp;
+        in.plain_only = env_plain_only(envp, opt);
+        const bool env_forms = envp && !in.plain_only;
         for (int k = 0; k < 3; k++)
-            in.grid[k] = envp ? env_grid(tab, leaf_one_kernel, simple) : path_grid[k][tab][leaf_one_kernel][simple];
+            in.grid[k] = env_forms ? env_form_grid(k, tab, leaf_one_kernel, simple)
+                                   : (envp ? env_grid(tab, leaf_one_kernel, simple) : path_grid[k][tab][leaf_one_kernel][simple]);
         in.block = kTraceBlock;
         const PathPlan pl = plan_path(in, opt);
         last_ppl1000 = pl.ppl1000;
@@ -1271,7 +1286,10 @@ struct akr_hip_ctx {
         const AKR_GLOBAL EnvDev *erec = envp ? env_rec(ms) : nullptr;  // copied before the timed launch, once per upload
         timed("path", ms, [&] {  // one timed record: a gated launch that exits at once adds microseconds
             for (int k = 0; k < pl.n_launch; k++) {
-                if (envp)
+                if (env_forms)
+                    launch_path_env_form(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, simple, PathEnvArgs{args[k], erec},
+                                         pl.launch[k].grid, ms);
+                else if (envp)
                     launch_path_env(opt.count, tab, leaf_one_kernel, simple, PathEnvArgs{args[k], erec}, pl.launch[k].grid, ms);
                 else
                     launch_path(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, simple, args[k], pl.launch[k].grid, ms);

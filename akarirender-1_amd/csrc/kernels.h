@@ -42,6 +42,11 @@ int path_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple);  // of t
 // with an environment light (option env_path): PATH_PLAIN's kernels over PathEnvArgs
 void launch_path_env(bool count, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid, hipStream_t st);
 int path_env_blocks_per_cu(bool tab, bool leaf_one, bool simple);
+// ... and every form's (option env_forms): PATH_DEFER / PATH_SPEC run k_path_defer_env /
+// k_path_spec_env, PATH_PLAIN is launch_path_env
+void launch_path_env_form(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid,
+                          hipStream_t st);
+int path_env_form_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple);
 bool path_tab_fits(int32_t n_mats, int32_t n_lights);
 void launch_check_weights(const float4 *film, uint32_t n, float expect, uint32_t *bad, hipStream_t st);
 void launch_merge_film(const float4 *film, const uint32_t *pixel, const uint32_t *order, uint32_t n, int32_t width,

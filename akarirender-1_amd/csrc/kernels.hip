@@ -12,6 +12,12 @@
 //   k_shade_mis, k_shade_env_mis, k_splat_mis
 //                      the same with multiple importance sampling of lights: NEE
 //                      weighted, the BSDF sample's share carried to whatever the extension ray finds
+//   k_path, k_path_defer, k_path_spec
+//                      the persistent path kernels: every sample of every pixel
+//                      in one launch
+//   k_path_env, k_path_defer_env, k_path_spec_env
+//                      the same with an environment light (options env_path and env_forms, DESIGN.md §3.17,
+//                      §0.8): k_shade_env's two terms inside the processing phase
 //
 // Numerics: f32 with the reference's operation order (akr_math.h); the library is built with
 // -ffp-contract=off and correctly rounded division/sqrt.
@@ -2709,8 +2715,13 @@ struct DeferState {
     __device__ __forceinline__ bool running() const { return get(RUN, 1) != 0; }
 };
 
-template <bool COUNT, bool TAB, bool SIMPLE>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_defer(PathArgs pa) {
+// ENV: the scene has an environment light (k_path_defer_env, option env_forms), entering as in
+// path_plain: the shading's branch of direct lighting, and the map at a camera ray's miss.  An environment
+// shadow ray (tmax = +inf, unoccluded when nothing is hit) is handed off, traced and posted like any other.
+// PathArgs comes by value: taken by reference, four of k_path_defer's and k_path_spec's twelve builds compiled to
+// other spill counts than they had as kernels of their own; by value one does.
+template <bool COUNT, bool TAB, bool SIMPLE, bool ENV = false>
+__device__ __forceinline__ void path_defer(const PathArgs pa, const EnvDev *env = nullptr) {
     if (pa.gate && *pa.gate != pa.gate_want) return;  // the other candidate form runs (uniform: before any barrier)
     const TraceArgs &a = pa.t;
     __shared__ unsigned long long s_stack_mem[kStackLdsU64];
@@ -2811,14 +2822,34 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                     }
                 } else {  // the running sample's closest hit
                     s.set(DeferState::KIND, 2, RAY_NONE);
+                    // ENV: the record's address passes through an empty asm here, as in path_plain, so its
+                    // fields are loaded in this phase and are not live across the traversal
+                    [[maybe_unused]] const EnvDev *envp = env;
+                    if constexpr (ENV) {
+                        unsigned long long eb = (unsigned long long)env;
+                        asm volatile("" : "+s"(eb));
+                        envp = (const EnvDev *)(const AKR_GLOBAL EnvDev *)eb;
+                    }
                     if (hgid == kNoHit) {
+                        if constexpr (ENV) {
+                            if (s.depth() == 0) {  // a camera ray that leaves the scene sees the map; deeper misses add nothing
+                                const V3 d{bitsf(s_park[3][tid]), bitsf(s_park[4][tid]), bitsf(s_park[5][tid])};
+                                int ti, tj;
+                                float len;
+                                env_encode(envp->n, env_to_map(*envp, d), ti, tj, len);
+                                const V3 e = mul(beta, env_lookup(*envp, ti, tj));
+                                Lr.x += e.x;
+                                Lr.y += e.y;
+                                Lr.z += e.z;
+                            }
+                        }
                         sample_end = true;
                     } else {
                         const V3 wo{-bitsf(s_park[3][tid]), -bitsf(s_park[4][tid]), -bitsf(s_park[5][tid])};
                         const int depth = s.depth();
                         Bounce bo;
-                        shade_hit_path<SIMPLE>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
-                                  pa.max_depth, depth == nb - 1, bo);
+                        shade_hit_path<SIMPLE, ENV>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth,
+                                  pa.max_depth, depth == nb - 1, bo, nullptr, envp);
                         if (bo.emit) {
                             Lr.x += bo.e.x;
                             Lr.y += bo.e.y;
@@ -2873,6 +2904,10 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 const uint32_t need = ((1u << k) - 1u) << (kDeferSlots * q);
                 const uint32_t res = s_res[tid];
                 if ((res & need) != need) break;
+                // Lr belongs to the sample that ended last, and only while no newer one runs: sound because a
+                // non-zero Lr is depth-0 emission or (ENV) the map at a camera ray's miss, and both end the
+                // sample at depth 0 with no shadow ray queued, so no newer sample starts (and clears Lr) before
+                // this one closes: it closes in step 2, or waits here behind one older sample with try_start barred
                 V3 L = (q == s.last() && !s.running()) ? Lr : V3{0.0f, 0.0f, 0.0f};
                 for (uint32_t b = 0; b < k; b++)  // pathtracer.h:84-88, in bounce order
                     if (!((res >> (16 + kDeferSlots * q + b)) & 1u)) {
@@ -3010,6 +3045,11 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
 
 #undef DEFER_SPLAT
 
+template <bool COUNT, bool TAB, bool SIMPLE>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_defer(PathArgs pa) {
+    path_defer<COUNT, TAB, SIMPLE>(pa);
+}
+
 // ------------------------------------------------------------- persistent path, speculative samples
 // k_path_spec: k_path whose lanes, once the pixel queue is drained, help the busy
 // pixels of their wave by running their later samples speculatively.  A pixel's samples are
@@ -3059,8 +3099,13 @@ struct SpecState {
     __device__ __forceinline__ uint32_t nh() const { return get(NH, 5); }
 };
 
-template <bool COUNT, bool TAB, bool SIMPLE>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_spec(PathArgs pa) {
+// ENV: the scene has an environment light (k_path_spec_env, option env_forms), entering as in
+// path_plain.  Under ENV the shading draws lu at every vertex, so a vertex still costs six draws and g_full /
+// g_one stay true; a camera miss (four draws) is neither guessed length and drops every node, as any other
+// length does.  A helper's speculative sample carries the miss term in its own Lr until its owner commits or
+// drops it.
+template <bool COUNT, bool TAB, bool SIMPLE, bool ENV = false>
+__device__ __forceinline__ void path_spec(const PathArgs pa, const EnvDev *env = nullptr) {
     if (pa.gate && *pa.gate != pa.gate_want) return;  // the other candidate form runs (uniform: before any barrier)
     const TraceArgs &a = pa.t;
     __shared__ unsigned long long s_stack_mem[kStackLdsU64];
@@ -3131,6 +3176,14 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                 fin = false;
                 bool sample_end = false;
                 const uint32_t hgid = r.bgid;
+                // ENV: the record's address passes through an empty asm here, as in path_plain, so its
+                // fields are loaded in this phase and are not live across the traversal
+                [[maybe_unused]] const EnvDev *envp = env;
+                if constexpr (ENV) {
+                    unsigned long long eb = (unsigned long long)env;
+                    asm volatile("" : "+s"(eb));
+                    envp = (const EnvDev *)(const AKR_GLOBAL EnvDev *)eb;
+                }
                 if (s.any()) {  // shadow ray: NEE contribution when unoccluded (pathtracer.h:84-88)
                     if (hgid == kNoHit) {
                         Lr.x += scol.x;
@@ -3146,11 +3199,24 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
                         sample_end = true;
                     }
                 } else if (hgid == kNoHit) {  // on_miss: the sample ends
+                    if constexpr (ENV) {
+                        if (depth == 0) {  // a camera ray that leaves the scene sees the map; deeper misses add nothing
+                            const V3 d{bitsf(s_park[3][tid]), bitsf(s_park[4][tid]), bitsf(s_park[5][tid])};
+                            int ti, tj;
+                            float len;
+                            env_encode(envp->n, env_to_map(*envp, d), ti, tj, len);
+                            const V3 e = mul(beta, env_lookup(*envp, ti, tj));
+                            Lr.x += e.x;
+                            Lr.y += e.y;
+                            Lr.z += e.z;
+                        }
+                    }
                     sample_end = true;
                 } else {
                     const V3 wo{-bitsf(s_park[3][tid]), -bitsf(s_park[4][tid]), -bitsf(s_park[5][tid])};
                     Bounce bo;
-                    shade_hit_path<SIMPLE>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth, pa.max_depth, depth == nb - 1, bo);
+                    shade_hit_path<SIMPLE, ENV>(pa.sc, tab, hgid, r.bu, r.bv, wo, beta, seed, depth, pa.max_depth, depth == nb - 1, bo,
+                                                nullptr, envp);
                     if (bo.emit) {
                         Lr.x += bo.e.x;
                         Lr.y += bo.e.y;
@@ -3482,6 +3548,11 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR
     }
     if (pa.fault_test && pa.fault && blockIdx.x == 0 && threadIdx.x == 0)
         __hip_atomic_fetch_or(pa.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <bool COUNT, bool TAB, bool SIMPLE>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_spec(PathArgs pa) {
+    path_spec<COUNT, TAB, SIMPLE>(pa);
 }
 
 // Film::merge_tile (core/film.h:85-95) on the device: a context's packed film (one float4 per
@@ -3831,6 +3902,17 @@ __global__ __launch_bounds__(kShadeBlock) void k_shade_env_spec_mis(ShadeEnvMisA
     shade_queue<true, true, true>(a.s, &a.env, &a.m);
 }
 
+// k_path_defer and k_path_spec with an environment light (option env_forms): the same bodies
+// over PathEnvArgs, as k_path_env is k_path's; named after every other kernel of this file for the same reason
+template <bool COUNT, bool TAB, bool SIMPLE>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_defer_env(PathEnvArgs ea) {
+    path_defer<COUNT, TAB, SIMPLE, true>(ea.p, (const EnvDev *)ea.env);
+}
+template <bool COUNT, bool TAB, bool SIMPLE>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(AKR_PATH_WAVES))) void k_path_spec_env(PathEnvArgs ea) {
+    path_spec<COUNT, TAB, SIMPLE, true>(ea.p, (const EnvDev *)ea.env);
+}
+
 // ------------------------------------------------------------------------------------ launch
 static inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
@@ -4004,6 +4086,32 @@ void launch_path_env(bool count, bool tab, bool leaf_one, bool simple, const Pat
 int path_env_blocks_per_cu(bool tab, bool leaf_one, bool simple) {
     int nb = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_env_kernel(false, tab, leaf_one, simple),
+                                                                      kTraceBlock, 0);
+    if (e != hipSuccess || nb <= 0) nb = 1;
+    return nb;
+}
+// PATH_DEFER's and PATH_SPEC's environment kernels (option env_forms), chosen as path_kernel() chooses theirs
+static PathEnvKernel path_env_form_kernel(int kind, bool count, bool tab, bool simple) {
+    if (kind == PATH_DEFER) {
+        if (count) return tab ? k_path_defer_env<true, true, false> : k_path_defer_env<true, false, false>;
+        if (simple) return tab ? k_path_defer_env<false, true, true> : k_path_defer_env<false, false, true>;
+        return tab ? k_path_defer_env<false, true, false> : k_path_defer_env<false, false, false>;
+    }
+    if (count) return tab ? k_path_spec_env<true, true, false> : k_path_spec_env<true, false, false>;
+    if (simple) return tab ? k_path_spec_env<false, true, true> : k_path_spec_env<false, false, true>;
+    return tab ? k_path_spec_env<false, true, false> : k_path_spec_env<false, false, false>;
+}
+void launch_path_env_form(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid,
+                          hipStream_t st) {
+    if (kind == PATH_PLAIN) return launch_path_env(count, tab, leaf_one, simple, a, grid, st);
+    if (grid == 0) return;
+    if (tab && !path_tab_fits(a.p.sc.n_mats, a.p.sc.n_lights)) tab = false;  // the LDS copy must hold every record
+    hipLaunchKernelGGL(path_env_form_kernel(kind, count, tab, simple), dim3(grid), dim3(kTraceBlock), 0, st, a);
+}
+int path_env_form_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple) {
+    if (kind == PATH_PLAIN) return path_env_blocks_per_cu(tab, leaf_one, simple);
+    int nb = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_env_form_kernel(kind, false, tab, simple),
                                                                       kTraceBlock, 0);
     if (e != hipSuccess || nb <= 0) nb = 1;
     return nb;

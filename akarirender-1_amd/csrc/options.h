@@ -31,6 +31,12 @@ struct Options {
     // build renders the scene (k_path_env), bit for bit what k_shade_env gives.
     // Off: every launch is the one it was
     bool env_path = false;
+    // option "env_forms" (default 0, read at every render and continue): with an environment set and env_path 1,
+    // the form rule of "path" decides as it does without an environment (path_defer / path_spec, the cache and
+    // tail rules, the gated launch), and k_path_defer's / k_path_spec's environment builds carry it out
+    // (k_path_defer_env, k_path_spec_env), bit for bit what k_shade_env gives.
+    // Off, or env_path 0, or no environment: every launch is the one it was
+    bool env_forms = false;
 
     // The render form of a constant-shading scene.  A "tail form"
     // (k_path_spec, or k_path_defer when path_spec is 0) pays where k_path's launch would end on a few
@@ -264,6 +270,11 @@ inline std::string set_option(Options &o, const char *key, int64_t value) {
     if (key && strcmp(key, "env_path") == 0) {  // a choice of form under an environment
         if (value != 0 && value != 1) return "env_path must be in [0, 1]";
         o.env_path = value == 1;
+        return {};
+    }
+    if (key && strcmp(key, "env_forms") == 0) {  // which persistent forms env_path may take
+        if (value != 0 && value != 1) return "env_forms must be in [0, 1]";
+        o.env_forms = value == 1;
         return {};
     }
     const OptionRow *r = find_option(key);

@@ -23,11 +23,16 @@ struct PathPlanIn {
     uint64_t bvh_dev_bytes = 0;   // the uploaded wide nodes + leaf blob
     uint32_t grid[3] = {0, 0, 0}; // resident workgroups of each kernel form [kind], for the render's `tab`
     uint32_t block = 256;         // threads per workgroup of the path kernels
-    // only PATH_PLAIN exists for this render (an environment light under option env_path):
-    // one ungated k_path launch whatever path_defer / path_spec and the cache rule say; the pilot, the cost
-    // order, subset lists, path_grid_pct and path_prio apply as for k_path
+    // only PATH_PLAIN is taken for this render (an environment light under option env_path without option
+    // env_forms): one ungated k_path launch whatever path_defer / path_spec and the cache rule
+    // say; the pilot, the cost order, subset lists, path_grid_pct and path_prio apply as for k_path.  With
+    // env_forms every form has an environment kernel and the flag stays false (env_plain_only)
     bool plain_only = false;
 };
+
+// PathPlanIn::plain_only of a persistent render: set under an environment unless option env_forms lifts it
+// (render_path() is reached under an environment only with option env_path on)
+inline bool env_plain_only(bool env_on, const Options &o) { return env_on && !o.env_forms; }
 
 // which list a launch fetches its slots through
 enum : int { LIST_NONE = 0, LIST_PILOT = 1, LIST_SUBSET = 2 };

@@ -243,9 +243,16 @@ int akr_hip_set_option(akr_hip_ctx *ctx, const char *key, int64_t value);
  * And a choice of form: "env_path" (0 or 1, default 0; read at every render and continue, like "path"; any other
  * value is refused).  An environment light keeps the wavefront form unless it is 1; with it on, "path" decides as
  * it does without an environment, and where it takes a persistent kernel, k_path's environment build renders the
- * scene (only k_path has one: "path_defer" and "path_spec" are not consulted).  The result is the
- * wavefront's bit for bit; akr_hip_render_form reports k_path.  "mis", exact_cull, "wide" 0 and a view outside the
- * lean test's bounds keep the wavefront as before.  Without an environment it changes nothing. */
+ * scene ("path_defer" and "path_spec" are not consulted unless "env_forms" is 1, below).  The
+ * result is the wavefront's bit for bit; akr_hip_render_form reports k_path.  "mis", exact_cull, "wide" 0 and a view
+ * outside the lean test's bounds keep the wavefront as before.  Without an environment it changes nothing.
+ * And which persistent forms it may take: "env_forms" (0 or 1, default 0; read at every render and continue; any
+ * other value is refused).  It acts only when an environment is set and "env_path" is 1: the render form rule then
+ * decides exactly as it does without an environment ("path_defer", "path_spec", the cache and tail rules, the gated
+ * launch of two candidates, subset lists), and k_path, k_path_defer and k_path_spec each have an environment build
+ * that carries the choice out.  The result is the same bit for bit; akr_hip_render_form reports
+ * the form that ran and akr_hip_render_shading its shading build.  With it 0, or "env_path" 0, or no environment,
+ * every launch is the one it was. */
 
 int akr_hip_upload_mesh(akr_hip_ctx *ctx, const float *vertices, uint64_t n_vertices,
                         const int32_t *indices, const float *normals, const float *texcoords,
