@@ -190,6 +190,8 @@ EXPORTS = {
     "akr_hip_accel_info": (C.c_int, [_P, C.POINTER(AccelInfo)]),
     "akr_hip_accel_export": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64]),
     "akr_hip_set_camera": (C.c_int, [_P, C.POINTER(Camera)]),
+    "akr_hip_set_lens": (C.c_int, [_P, C.c_float, C.c_float]),
+    "akr_hip_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "akr_hip_trace": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_int]),
     "akr_hip_trace_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_int, _P]),
     "akr_hip_render": (C.c_int, [_P, C.POINTER(PtParams), _P, C.c_int32, _P, _P]),
@@ -501,6 +503,17 @@ class HipContext:
         cam = Camera((C.c_float * 3)(*position), (C.c_float * 3)(*rotation_deg), float(fov_deg),
                      (C.c_int32 * 2)(*resolution))
         self._check(self.lib.akr_hip_set_camera(self.h, C.byref(cam)))
+
+    def set_lens(self, radius, focal):
+        """The thin lens (kernel/camera.h:43-44, 75-80): lens_radius and focal_distance, both finite and >= 0;
+        (0, 0) is the pinhole.  Active when both are > 0; renders then take the wavefront form."""
+        self._check(self.lib.akr_hip_set_lens(self.h, float(radius), float(focal)))
+
+    def lens(self):
+        """(lens_radius, focal_distance, active) as the context holds them."""
+        r, f, a = C.c_float(0), C.c_float(0), C.c_int32(0)
+        self._check(self.lib.akr_hip_lens(self.h, C.byref(r), C.byref(f), C.byref(a)))
+        return float(r.value), float(f.value), bool(a.value)
 
     def trace(self, rays: np.ndarray, any_hit: bool = False) -> np.ndarray:
         rays = np.ascontiguousarray(rays, RAY_DTYPE)

@@ -174,6 +174,9 @@ def scene_fingerprint(cs, mis: bool = False) -> str:
     add("cam_rotation", cam.rotation, np.float32)
     add("cam_fov", [cam.fov], np.float64)
     add("cam_resolution", cam.resolution, np.int32)
+    lens = (np.float32(getattr(cam, "lens_radius", 0.0)), np.float32(getattr(cam, "focal_distance", 0.0)))
+    if lens[0] > 0 and lens[1] > 0:  # an inactive lens is the pinhole: it keeps the fingerprint it always had
+        add("cam_lens", lens, np.float32)
     if mis:  # a render without it keeps the fingerprint it always had
         add("mis", [1], np.int32)
     env = getattr(cs, "environment", None)

@@ -34,6 +34,10 @@ kernel renders the scene where the render form rule takes it.
 --env-forms (with --env-path) sets library option "env_forms" on every context as well: the form rule then
 chooses among k_path, k_path_defer and k_path_spec as it does without an environment, which
 is what a rank's share of a --gpus N render takes.  The image is the same.
+       ... --lens-radius R (--focal-distance D | --focus-at X Y)
+A thin-lens camera: depth of field around the plane at distance D along the view axis, or
+around what the centre of pixel (X, Y) sees.  The camera node's lens_radius and focal_distance do the same;
+every line above works with it, --denoise and --gpus N included.
 """
 from __future__ import annotations
 
@@ -46,7 +50,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import capi, denoise, envmap, film, progressive, scene
+from . import capi, denoise, envmap, film, lens, progressive, scene
 from .dist import tile_grid
 
 
@@ -298,7 +302,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          "as it does without an environment (library option env_forms); the image is the same")
     ap.add_argument("--env-res", type=int, default=None, metavar="N",
                     help="resolution of the octahedral map made from a lat-long image, 1..2048")
+    ap.add_argument("--lens-radius", type=float, default=None, metavar="R",
+                    help="thin-lens camera: the lens radius in scene units (0: pinhole); replaces the camera's "
+                         "lens_radius")
+    ap.add_argument("--focal-distance", type=float, default=None, metavar="D",
+                    help="thin-lens camera: the distance of the plane of focus along the view axis; replaces the "
+                         "camera's focal_distance")
+    ap.add_argument("--focus-at", type=int, nargs=2, default=None, metavar=("X", "Y"),
+                    help="thin-lens camera: focus on what the centre of pixel (X, Y) sees")
     args = ap.parse_args(argv)
+    for name, v in (("--lens-radius", args.lens_radius), ("--focal-distance", args.focal_distance)):
+        if v is not None and not (math.isfinite(v) and v >= 0):  # refused before the scene is read
+            ap.error(f"{name} needs a finite number >= 0")
+    if args.focus_at is not None and args.focal_distance is not None:
+        ap.error("--focus-at cannot be combined with --focal-distance")
     if args.env_res is not None and not 1 <= args.env_res <= 2048:  # refused before the scene is read
         ap.error("--env-res needs 1..2048")
     if args.env_scale is not None and not args.env_scale >= 0:
@@ -374,6 +391,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if passes and not isinstance(sc.integrator, scene.PathIntegrator):
         ap.error(f"--pass-spp, --preview, --time-budget, --checkpoint, --resume and --adaptive need the Path integrator; "
                  f"the scene's is {type(sc.integrator).__name__}")
+    cam = sc.camera
+    if args.lens_radius is not None:
+        cam.lens_radius = float(np.float32(args.lens_radius))
+    if args.focal_distance is not None:
+        cam.focal_distance = float(np.float32(args.focal_distance))
+    if args.focus_at is not None:  # a probe ray on the first device, before the render's contexts exist
+        try:
+            with capi.HipContext(0) as probe:
+                scene.upload_scene(probe, scene.compile_scene(sc))
+                cam.focal_distance = lens.autofocus(probe, cam, *args.focus_at)
+        except ValueError as e:
+            ap.error(str(e))
+        print(f"focus at pixel ({args.focus_at[0]}, {args.focus_at[1]}): focal distance {cam.focal_distance:.9g}",
+              flush=True)
+    if cam.lens_radius > 0 and not cam.focal_distance > 0:
+        ap.error("a lens radius > 0 needs a focal distance > 0 (--focal-distance, --focus-at or the camera's field)")
     out = args.out or sc.output
     t0 = time.time()
 

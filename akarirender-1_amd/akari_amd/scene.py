@@ -95,6 +95,10 @@ class PerspectiveCamera:        # core/nodes/camera.cpp:26-52 (fov default radia
     rotation: Sequence[float] = (0.0, 0.0, 0.0)   # degrees
     fov: float = 80.0                               # degrees
     resolution: Sequence[int] = (512, 512)
+    # the thin lens of kernel/camera.h:43-44, which the reference's node never sets: active
+    # when both are > 0, a pinhole otherwise
+    lens_radius: float = 0.0
+    focal_distance: float = 0.0
 
 
 @dataclass
@@ -398,6 +402,7 @@ def upload_scene(ctx: "capi.HipContext", cs: CompiledScene, build: bool = True, 
     upload_environment(ctx, cs.environment)
     cam = cs.camera
     ctx.set_camera(cam.position, cam.rotation, cam.fov, cam.resolution)
+    upload_lens(ctx, cam)
     if bvh is not None:
         return ctx.import_accel(bvh[0], bvh[1], n_threads=build_kw.get("n_threads", 0))
     if build:
@@ -411,6 +416,15 @@ def upload_environment(ctx: "capi.HipContext", env: Optional[CompiledEnvironment
         ctx.upload_environment(env.map, env.scale, env.select_prob, env.world_to_env)
     elif hasattr(ctx.lib, "akr_hip_upload_environment"):   # an experiment library may predate the entry point
         ctx.upload_environment(None)
+
+
+def upload_lens(ctx: "capi.HipContext", cam: PerspectiveCamera):
+    """The camera's lens, or zeros for a pinhole, so that a reused context loses the last scene's lens."""
+    r, f = float(getattr(cam, "lens_radius", 0.0)), float(getattr(cam, "focal_distance", 0.0))
+    if hasattr(ctx.lib, "akr_hip_set_lens"):   # an experiment library may predate the entry point
+        ctx.set_lens(r, f)
+    elif r > 0 and f > 0:
+        raise RuntimeError("this library has no akr_hip_set_lens: the scene's lens cannot be rendered")
 
 
 # ----------------------------------------------------------------------------- .akari loader
@@ -647,6 +661,16 @@ class SdlParser:
                 cam.position = tuple(float(F32(x)) for x in f["position"])
             if "resolution" in f:
                 cam.resolution = tuple(int(x) for x in f["resolution"])
+            for k in ("lens_radius", "focal_distance"):
+                if k in f:
+                    v = f[k]
+                    if isinstance(v, bool) or not isinstance(v, (int, float)):
+                        self._err(f"PerspectiveCamera: {k} is a number")
+                    if not (math.isfinite(v) and math.isfinite(float(F32(v))) and v >= 0):
+                        self._err(f"PerspectiveCamera: {k} {v} is not a finite number >= 0")
+                    setattr(cam, k, float(F32(v)))
+            if cam.lens_radius > 0 and not cam.focal_distance > 0:
+                self._err("PerspectiveCamera: lens_radius > 0 needs a focal_distance > 0")
             return cam
         if t == "DiffuseMaterial":
             return DiffuseMaterial(self._texture(f.get("color", 0.0)))

@@ -268,6 +268,13 @@ class HipPathTracer {
         check(scene.handle(), akr_hip_upload_environment(scene.handle(), nullptr, nullptr), "upload_environment");
     }
 
+    // Thin lens (include/akr_hip.h): PerspectiveCamera's lens_radius and focal_distance
+    // (kernel/camera.h:43-44, 75-80), both finite and >= 0; (0, 0) is the pinhole.  With both > 0 the renders take
+    // the wavefront form.  Ends the render session; HipAccelerator::build (akr_hip_set_camera) leaves it alone.
+    static void set_lens(const HipAccelerator &scene, float radius, float focal) {
+        check(scene.handle(), akr_hip_set_lens(scene.handle(), radius, focal), "set_lens");
+    }
+
     // Render sessions (include/akr_hip.h): the accelerator's context remembers its last render(), and
     // render_continue adds `more` samples per pixel from where it stopped; the film is cleared and then
     // holds the session's totals, bit for bit the film of one render() of all the samples.

@@ -317,6 +317,16 @@ struct RaygenArgs {
     uint32_t slot_base;            // without `order`: queue position i holds slot slot_base + i
 };
 
+// The thin lens (kernel/camera.h:43-44): beside CameraDev, for the lens kernels only
+struct LensDev {
+    float radius, focal;           // lens_radius, focal_distance: both > 0 where a lens kernel is launched
+};
+
+struct RaygenLensArgs {
+    RaygenArgs r;
+    LensDev lens;
+};
+
 struct SplatArgs {
     float4 *L;
     float4 *film;

@@ -221,6 +221,15 @@ struct akr_hip_ctx {
 
     CameraDev cam{};
     bool cam_set = false;
+    // The thin lens, akr_hip_set_lens: (0, 0) is the pinhole.  Where it is active the camera
+    // rays of the wavefront render, the AO render and the feature pass come from the lens kernels, and render()
+    // takes the wavefront form; the context's lens decides at every call, continues included.
+    LensDev lens{0.0f, 0.0f};
+    bool lens_active() const { return lens.radius > 0 && lens.focal > 0; }  // camera.h:75
+    void raygen_launch(const RaygenArgs &rg, hipStream_t st) {
+        if (lens_active()) launch_raygen_lens(RaygenLensArgs{rg, lens}, st);
+        else launch_raygen(rg, st);
+    }
 
     // Environment light: the map and the tables of its distribution, built by
     // akr_hip_upload_environment; env.n == 0: none.  A scene with one renders in the wavefront form.
@@ -1163,7 +1172,9 @@ struct akr_hip_ctx {
         // and so does option "mis": its kernels are the wavefront's
         const bool env_wavefront = env_on() && !opt.env_path;
         // and so does a scene that holds a Mirror or a Glass: k_shade_spec and its forms
-        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_wavefront && !mis_on && !spec_on) {
+        // and so does an active thin lens: k_raygen_lens is the wavefront's
+        if (use_path && tight && opt.wide && trace_args(nullptr).lean && !env_wavefront && !mis_on && !spec_on &&
+            !lens_active()) {
             if (p.spp > 0) render_path(pass);
             last_passes = 1;
         } else {
@@ -1349,7 +1360,7 @@ struct akr_hip_ctx {
             RaygenArgs rg = raygen_args((uint32_t)M, L, qcount(0), s == 0 && !resume);
             rg.probe = probe_p;
             rg.order = subset ? subset : worder;
-            timed("raygen", ms, [&] { launch_raygen(rg, ms); });
+            timed("raygen", ms, [&] { raygen_launch(rg, ms); });
             for (int b = 0; b < nb; b++, g++) {
                 const bool odd = b & 1;
                 const int sq = (int)(g & 1);
@@ -1471,7 +1482,7 @@ struct akr_hip_ctx {
             if (s >= 2) HIPCHK(hipStreamWaitEvent(ms, ev_splat[ps], 0));
             HIPCHK(hipMemsetAsync(cnt, 0, n_count_words * sizeof(uint32_t), ms));
             const RaygenArgs rg = raygen_args((uint32_t)N, L, qcount, s == 0);
-            timed("raygen", ms, [&] { launch_raygen(rg, ms); });
+            timed("raygen", ms, [&] { raygen_launch(rg, ms); });
             TraceArgs t = trace_args(work0);
             t.rays = d_ray0.p;
             t.count = qcount;
@@ -1556,7 +1567,10 @@ struct akr_hip_ctx {
         HIPCHK(hipMemsetAsync(d_ft_acc.p, 0, 3 * N * sizeof(float4), st));
         const bool tight = !(opt.exact_cull || (p.flags & AKR_PT_EXACT_CULL));
         for (int s = 0; s < p.spp; s++) {
-            timed("feature_rays", st, [&] { launch_feature_rays(cam, d_ft_pixel.p, (uint32_t)N, d_ft_seed.p, s == 0, rays, st); });
+            timed("feature_rays", st, [&] {
+                if (lens_active()) launch_feature_rays_lens(cam, lens, d_ft_pixel.p, (uint32_t)N, d_ft_seed.p, s == 0, rays, st);
+                else launch_feature_rays(cam, d_ft_pixel.p, (uint32_t)N, d_ft_seed.p, s == 0, rays, st);
+            });
             HIPCHK(hipMemsetAsync(d_work.p, 0, kTraceWords * sizeof(uint32_t), st));
             TraceArgs t = trace_args(d_work.p);
             t.rays = rays;
@@ -2162,6 +2176,27 @@ int akr_hip_set_camera(akr_hip_ctx *ctx, const akr_camera *camera) {
         ctx->cam = make_camera(*camera);
         ctx->cam_set = true;
         ctx->drop_session();
+    });
+}
+
+int akr_hip_set_lens(akr_hip_ctx *ctx, float lens_radius, float focal_distance) {
+    return guard(ctx, [&] {
+        // checked before anything is stored: a refused call leaves the lens and the session as they were
+        if (!std::isfinite(lens_radius) || lens_radius < 0)
+            throw std::runtime_error("set_lens: lens_radius must be finite and >= 0 (got " + std::to_string(lens_radius) + ")");
+        if (!std::isfinite(focal_distance) || focal_distance < 0)
+            throw std::runtime_error("set_lens: focal_distance must be finite and >= 0 (got " +
+                                     std::to_string(focal_distance) + ")");
+        ctx->lens = LensDev{lens_radius, focal_distance};
+        ctx->drop_session();
+    });
+}
+
+int akr_hip_lens(akr_hip_ctx *ctx, float *lens_radius, float *focal_distance, int32_t *active) {
+    return guard(ctx, [&] {
+        if (lens_radius) *lens_radius = ctx->lens.radius;
+        if (focal_distance) *focal_distance = ctx->lens.focal;
+        if (active) *active = ctx->lens_active() ? 1 : 0;
     });
 }
 

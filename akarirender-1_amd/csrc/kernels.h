@@ -89,6 +89,10 @@ void launch_adaptive_test(const float4 *film, float4 *prev, uint32_t n, float th
 void launch_feature_rays(const CameraDev &cam, const uint32_t *pixel, uint32_t n, uint32_t *seed, bool first,
                          float4 *rays, hipStream_t st);
 void launch_feature_shade(const FeatureArgs &a, hipStream_t st);
+// with an active thin lens: k_raygen's and k_feature_rays' lens forms
+void launch_raygen_lens(const RaygenLensArgs &a, hipStream_t st);
+void launch_feature_rays_lens(const CameraDev &cam, const LensDev &lens, const uint32_t *pixel, uint32_t n, uint32_t *seed,
+                              bool first, float4 *rays, hipStream_t st);
 
 // edge-avoiding a-trous filter of the film (denoise.hip): frame-ordered buffers of n = W * H
 // pixels; guide = 3 float4 per pixel (unit normal | depth, position | 0, albedo | 0), I = (colour | state)

@@ -933,8 +933,13 @@ __device__ __forceinline__ void apply_rows(const float *m, float x, float y, flo
 }
 
 // camera_ray: generate_ray(next2d() /*lens*/, next2d() /*film*/, p) — pathtracer.h:61-64
-__device__ __forceinline__ void camera_ray(const CameraDev &cam, int x, int y, uint32_t &seed, float4 &r0, float4 &r1) {
-    lcg_next2(seed);
+// LENS: the thin lens of camera.h:75-80 compiled in without its test (the host launches that build only when
+// lens_radius > 0 && focal_distance > 0); without it the lens draw is made and unused
+template <bool LENS = false>
+__device__ __forceinline__ void camera_ray(const CameraDev &cam, int x, int y, uint32_t &seed, float4 &r0, float4 &r1,
+                                           const LensDev lens = LensDev{}) {
+    const V2 u1 = lcg_next2(seed);
+    (void)u1;
     const V2 u2 = lcg_next2(seed);
     const float pfx = (float)x + u2.x, pfy = (float)y + u2.y;
     float r[4];
@@ -945,8 +950,17 @@ __device__ __forceinline__ void camera_ray(const CameraDev &cam, int x, int y, u
         py_ = py_ / r[3];
     }
     V3 d = normalize(v3(px_ - 0.0f, py_ - 0.0f, 0.0f - 1.0f));
+    V3 oc = v3(0.0f, 0.0f, 0.0f);
+    if constexpr (LENS) {
+        const V2 dk = concentric_disk(u1);
+        const float plx = dk.x * lens.radius, ply = dk.y * lens.radius;  // p_lens, camera.h:69
+        const float ft = lens.focal / fabsf(d.z);
+        const V3 p_focus = add(oc, muls(d, ft));  // ray(ft) = o + t * d with o = (0, 0, 0)
+        oc = v3(plx, ply, 0.0f);
+        d = normalize(sub(p_focus, oc));
+    }
     float ro[4];
-    apply_rows(cam.c2w, 0.0f, 0.0f, 0.0f, 1.0f, ro, 4);
+    apply_rows(cam.c2w, oc.x, oc.y, oc.z, 1.0f, ro, 4);
     V3 o = v3(ro[0], ro[1], ro[2]);
     if (ro[3] != 1.0f) o = divs(o, ro[3]);
     float rd[3];
@@ -3902,6 +3916,43 @@ __global__ __launch_bounds__(kShadeBlock) void k_shade_env_spec_mis(ShadeEnvMisA
     shade_queue<true, true, true>(a.s, &a.env, &a.m);
 }
 
+// ------------------------------------------------------------------------------- thin lens
+// k_raygen and k_feature_rays over camera_ray<true>: the same draws, queues and stores, the
+// ray leaves a point of the lens towards the pinhole ray's point on the plane of focus.  After every other
+// plain kernel of this file, as k_shade_spec is and for the same reason.
+__global__ __launch_bounds__(kBlock) void k_raygen_lens(RaygenLensArgs la) {
+    const RaygenArgs &a = la.r;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t sl = a.order ? a.order[i] : a.slot_base + i;
+    const uint32_t px = a.pixel[sl];
+    const int x = (int)(px & 0xFFFFu), y = (int)(px >> 16);
+    uint32_t seed = a.first_pass ? (uint32_t)(x + y * a.cam.width) : a.seed[sl];
+    float4 r0, r1;
+    camera_ray<true>(a.cam, x, y, seed, r0, r1, la.lens);
+    a.L[sl] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    a.ray_out[2 * (size_t)i] = r0;
+    a.ray_out[2 * (size_t)i + 1] = r1;
+    a.state_out[i] = make_float4(1.0f, 1.0f, 1.0f, bitsf(seed));
+    a.slot_out[i] = sl;
+    if (a.probe) a.probe[sl].y += 1u;
+    if (i == 0) *a.count_out = a.n;
+}
+
+__global__ __launch_bounds__(kBlock) void k_feature_rays_lens(CameraDev cam, LensDev lens, const uint32_t *pixel, uint32_t n,
+                                                              uint32_t *seed, int32_t first, float4 *rays) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t px = pixel[i];
+    const int x = (int)(px & 0xFFFFu), y = (int)(px >> 16);
+    uint32_t s = first ? (uint32_t)(x + y * cam.width) : seed[i];
+    float4 r0, r1;
+    camera_ray<true>(cam, x, y, s, r0, r1, lens);
+    rays[2 * (size_t)i] = r0;
+    rays[2 * (size_t)i + 1] = r1;
+    seed[i] = s;
+}
+
 // k_path_defer and k_path_spec with an environment light (option env_forms): the same bodies
 // over PathEnvArgs, as k_path_env is k_path's; named after every other kernel of this file for the same reason
 template <bool COUNT, bool TAB, bool SIMPLE>
@@ -4187,6 +4238,17 @@ void launch_feature_rays(const CameraDev &cam, const uint32_t *pixel, uint32_t n
 }
 void launch_feature_shade(const FeatureArgs &a, hipStream_t st) {
     if (a.n) hipLaunchKernelGGL(k_feature_shade, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
+}
+// the thin lens: the caller launches these only for a lens with radius > 0 and focal > 0
+void launch_raygen_lens(const RaygenLensArgs &a, hipStream_t st) {
+    if (a.r.n == 0) return;
+    hipLaunchKernelGGL(k_raygen_lens, dim3(blocks_for(a.r.n)), dim3(kBlock), 0, st, a);
+}
+void launch_feature_rays_lens(const CameraDev &cam, const LensDev &lens, const uint32_t *pixel, uint32_t n, uint32_t *seed,
+                              bool first, float4 *rays, hipStream_t st) {
+    if (n)
+        hipLaunchKernelGGL(k_feature_rays_lens, dim3(blocks_for(n)), dim3(kBlock), 0, st, cam, lens, pixel, n, seed,
+                           first ? 1 : 0, rays);
 }
 
 }  // namespace akr

@@ -303,6 +303,20 @@ int akr_hip_accel_info(akr_hip_ctx *ctx, akr_accel_info *info);
 int akr_hip_accel_export(akr_hip_ctx *ctx, void *nodes, uint64_t node_bytes, void *tris,
                          uint64_t tri_bytes);
 int akr_hip_set_camera(akr_hip_ctx *ctx, const akr_camera *camera);
+/* The thin lens of the reference's kernel camera (kernel/camera.h:43-44, 75-80): lens_radius and
+ * focal_distance, which its camera node never sets.  Both must be finite and >= 0; any other value fails,
+ * names the value and leaves the context as it was.  (0, 0) is the pinhole and the state of a new context.
+ * The lens is active when both are > 0 (camera.h:75): a camera ray then leaves the point
+ * concentric_disk(u1) * lens_radius of the lens towards the point where the pinhole ray meets the plane
+ * z = -focal_distance of camera space.  u1 is the draw every sample already makes ahead of the film draw,
+ * so no sampler state changes.  With an active lens akr_hip_render runs the wavefront form whatever the
+ * options "path", "env_path", "env_forms" and "path_auto_complex" say (akr_hip_render_form reports it), and
+ * akr_hip_render_ao and the feature pass use the same rays; the cost-order pilot keeps pinhole rays.
+ * akr_hip_set_lens ends the render session, as akr_hip_set_camera does; akr_hip_set_camera leaves the lens
+ * alone.  akr_camera and AKR_HIP_API_VERSION are unchanged. */
+int akr_hip_set_lens(akr_hip_ctx *ctx, float lens_radius, float focal_distance);
+/* Reads the lens back (any pointer may be null); *active is 1 under the reference's condition above. */
+int akr_hip_lens(akr_hip_ctx *ctx, float *lens_radius, float *focal_distance, int32_t *active);
 
 /* Batched trace, host buffers in and out, synchronous. */
 int akr_hip_trace(akr_hip_ctx *ctx, const akr_ray *rays, uint64_t n, akr_hit *hits, int any_hit);
