@@ -381,26 +381,15 @@ struct akr_hip_ctx {
     DBuf<uint32_t> d_work;  // dynamic-fetch counters of a standalone trace launch (kTraceWords)
     uint32_t ovf_threads = 0;
     uint32_t trace_grid[3] = {0, 0, 0};
-    // resident workgroups of the persistent path kernels' product builds [kind][tab][leaf_one][simple]: of the
-    // kernel launch_path() launches for them
-    uint32_t path_grid[3][2][2][2] = {};
-    // the same of k_path's environment builds [tab][leaf_one][simple] (launch_path_env), queried when option
-    // env_path first renders with one; never above the grid the overflow stacks are sized for
-    uint32_t path_env_grid[2][2][2] = {};
-    uint32_t env_grid(bool tab, bool leaf_one, bool simple) {
-        uint32_t &g = path_env_grid[tab][leaf_one][simple];
-        if (!g) g = std::min<uint32_t>((uint32_t)(n_cu * path_env_blocks_per_cu(tab, leaf_one, simple)), ovf_threads / kTraceBlock);
-        return g;
-    }
-    // the same of k_path_defer's and k_path_spec's environment builds [kind][tab][simple] (launch_path_env_form),
-    // queried when option env_forms first renders with one; PATH_PLAIN is env_grid()
-    uint32_t path_env_form_grid[3][2][2] = {};
-    uint32_t env_form_grid(int kind, bool tab, bool leaf_one, bool simple) {
-        if (kind == PATH_PLAIN) return env_grid(tab, leaf_one, simple);
-        uint32_t &g = path_env_form_grid[kind][tab][simple];
-        if (!g)
-            g = std::min<uint32_t>((uint32_t)(n_cu * path_env_form_blocks_per_cu(kind, tab, leaf_one, simple)),
-                                   ovf_threads / kTraceBlock);
+    // resident workgroups of the persistent path kernels' product builds, by build_index (path_build.h): a
+    // counting launch runs on its product build's grid.  ensure_trace_grid() fills every build without an
+    // environment; an environment build (options env_path, env_forms) is queried when it first renders, and is
+    // never above the grid the overflow stacks are sized for
+    uint32_t path_grid[kPathBuilds] = {};
+    uint32_t grid_of(PathBuild b) {
+        b.count = false;
+        uint32_t &g = path_grid[build_index(b)];
+        if (!g) g = std::min<uint32_t>((uint32_t)(n_cu * path_blocks_per_cu(b)), ovf_threads / kTraceBlock);
         return g;
     }
     // the render form rule is plan_path() in path_plan.h; its knobs are in `opt`
@@ -676,10 +665,11 @@ struct akr_hip_ctx {
             mx = std::max(mx, trace_grid[m]);
         }
         for (int d = 0; d < 3; d++)
-            for (int k = 0; k < 8; k++) {
-                const int t = k >> 2, l = (k >> 1) & 1, s = k & 1;
-                path_grid[d][t][l][s] = (uint32_t)(n_cu * path_blocks_per_cu(d, t != 0, l != 0, s != 0));
-                mx = std::max(mx, path_grid[d][t][l][s]);
+            for (int k = 0; k < 8; k++) {  // every key without an environment; keys that share a build meet again
+                const PathBuild b{d, false, (k & 4) != 0, (k & 2) != 0, (k & 1) != 0, false};
+                uint32_t &g = path_grid[build_index(b)];
+                if (!g) g = (uint32_t)(n_cu * path_blocks_per_cu(b));
+                mx = std::max(mx, g);
             }
         ovf_threads = mx * kTraceBlock;
         d_ovf.reserve((size_t)ovf_threads * (kStackMax - kStackLds));
@@ -866,12 +856,12 @@ struct akr_hip_ctx {
         pp.order = nullptr;
         pp.fault_test = 0;
         pp.state_in = pp.state_out = nullptr;
+        const bool envp = env_on();
         const uint32_t grid = (uint32_t)std::max<uint64_t>(
-            1, std::min<uint64_t>(env_on() ? env_grid(tab, true, true) : path_grid[PATH_PLAIN][tab][1][1],
+            1, std::min<uint64_t>(grid_of(PathBuild{PATH_PLAIN, false, tab, true, true, envp}),
                                   ((uint64_t)N + kTraceBlock - 1) / kTraceBlock));
         // counting: the general shading
-        if (env_on()) launch_path_env(true, tab, leaf_one_kernel, false, PathEnvArgs{pp, env_rec(ms)}, grid, ms);
-        else launch_path(true, PATH_PLAIN, tab, leaf_one_kernel, false, pp, grid, ms);
+        launch_path(PathBuild{PATH_PLAIN, true, tab, leaf_one_kernel, false, envp}, pp, envp ? env_rec(ms) : nullptr, grid, ms);
         HIPCHK(hipMemsetAsync(d_film.p, 0, (size_t)N * sizeof(float4), ms));
     }
 
@@ -1255,10 +1245,11 @@ struct akr_hip_ctx {
         // the plan out
         const bool envp = env_on();
         in.plain_only = env_plain_only(envp, opt);
-        const bool env_forms = envp && !in.plain_only;
-        for (int k = 0; k < 3; k++)
-            in.grid[k] = env_forms ? env_form_grid(k, tab, leaf_one_kernel, simple)
-                                   : (envp ? env_grid(tab, leaf_one_kernel, simple) : path_grid[k][tab][leaf_one_kernel][simple]);
+        // plain_only: the rule plans no kind but PATH_PLAIN, whose build stands in for every kind's
+        auto build = [&](int kind) {
+            return PathBuild{in.plain_only ? PATH_PLAIN : kind, opt.count, tab, leaf_one_kernel, simple, envp};
+        };
+        for (int k = 0; k < 3; k++) in.grid[k] = grid_of(build(k));
         in.block = kTraceBlock;
         const PathPlan pl = plan_path(in, opt);
         last_ppl1000 = pl.ppl1000;
@@ -1296,15 +1287,7 @@ struct akr_hip_ctx {
         }
         const AKR_GLOBAL EnvDev *erec = envp ? env_rec(ms) : nullptr;  // copied before the timed launch, once per upload
         timed("path", ms, [&] {  // one timed record: a gated launch that exits at once adds microseconds
-            for (int k = 0; k < pl.n_launch; k++) {
-                if (env_forms)
-                    launch_path_env_form(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, simple, PathEnvArgs{args[k], erec},
-                                         pl.launch[k].grid, ms);
-                else if (envp)
-                    launch_path_env(opt.count, tab, leaf_one_kernel, simple, PathEnvArgs{args[k], erec}, pl.launch[k].grid, ms);
-                else
-                    launch_path(opt.count, pl.launch[k].kind, tab, leaf_one_kernel, simple, args[k], pl.launch[k].grid, ms);
-            }
+            for (int k = 0; k < pl.n_launch; k++) launch_path(build(pl.launch[k].kind), args[k], erec, pl.launch[k].grid, ms);
         });
         HIPCHK(hipGetLastError());
         last_shading = simple ? AKR_SHADING_SIMPLE : AKR_SHADING_GENERAL;
@@ -1404,18 +1387,7 @@ struct akr_hip_ctx {
                 sv.flag_in = odd ? d_spec_flag[1].p : d_spec_flag[0].p;
                 sv.flag_out = odd ? d_spec_flag[0].p : d_spec_flag[1].p;
                 sv.E = d_E[ps].p;
-                if (spec_on && mis_on && env_on())
-                    timed("shade", ms, [&] { launch_shade_env_spec_mis(ShadeEnvMisArgs{sh, env, md}, (uint32_t)M, ms); });
-                else if (spec_on && mis_on)
-                    timed("shade", ms, [&] { launch_shade_spec_mis(ShadeMisArgs{sh, md}, (uint32_t)M, ms); });
-                else if (spec_on && env_on())
-                    timed("shade", ms, [&] { launch_shade_env_spec(ShadeEnvSpecArgs{sh, env, sv}, (uint32_t)M, ms); });
-                else if (spec_on) timed("shade", ms, [&] { launch_shade_spec(ShadeSpecArgs{sh, sv}, (uint32_t)M, ms); });
-                else if (mis_on && env_on())
-                    timed("shade", ms, [&] { launch_shade_env_mis(ShadeEnvMisArgs{sh, env, md}, (uint32_t)M, ms); });
-                else if (mis_on) timed("shade", ms, [&] { launch_shade_mis(ShadeMisArgs{sh, md}, (uint32_t)M, ms); });
-                else if (env_on()) timed("shade", ms, [&] { launch_shade_env(ShadeEnvArgs{sh, env}, (uint32_t)M, ms); });
-                else timed("shade", ms, [&] { launch_shade(sh, (uint32_t)M, ms); });
+                timed("shade", ms, [&] { launch_shade(ShadeBuild{env_on(), mis_on, spec_on}, sh, &env, &md, &sv, (uint32_t)M, ms); });
                 HIPCHK(hipEventRecord(ev_shade[sq], ms));
                 HIPCHK(hipStreamWaitEvent(side, ev_shade[sq], 0));
                 if (b < p.max_depth) {

@@ -1,6 +1,7 @@
 // kernels.h — host-side launchers of the gfx950 kernels (kernels.hip).
 #pragma once
 #include "akr_device.h"
+#include "path_build.h"
 
 namespace akr {
 
@@ -12,41 +13,25 @@ enum : int { TRACE_CLOSEST = 0, TRACE_ANY = 1, TRACE_SHADOW = 2, TRACE_PILOT = 3
 void launch_trace(int mode, bool count, bool tight, bool wide, const TraceArgs &a, uint32_t grid, hipStream_t st);
 int trace_blocks_per_cu(int mode);
 void launch_raygen(const RaygenArgs &a, hipStream_t st);
-void launch_shade(const ShadeArgs &a, uint32_t max_items, hipStream_t st);
+// the wavefront shade kernel of a build (path_build.h): k_shade[_env][_spec][_mis].  env, m and d are read only
+// where the build has them: an environment light, multiple importance sampling of lights
+// (§3.18), a Mirror or a Glass in the scene (§3.19; under MIS the specular forms take m alone).  The film of the
+// MIS and specular forms is splatted by launch_splat_mis over MisDev::E or SpecDev::E
+void launch_shade(ShadeBuild b, const ShadeArgs &s, const EnvDev *env, const MisDev *m, const SpecDev *d, uint32_t max_items,
+                  hipStream_t st);
 void launch_splat(const SplatArgs &a, uint32_t max_items, hipStream_t st);
-// with an environment light: k_shade's environment form, and the unit kernels of
-// akr_hip_environment_sample (sample) / akr_hip_environment_eval
-void launch_shade_env(const ShadeEnvArgs &a, uint32_t max_items, hipStream_t st);
-// with multiple importance sampling of lights: the shade kernels' MIS forms and their splat
-void launch_shade_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st);
-void launch_shade_env_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st);
 void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st);
-// for scenes that hold a Mirror or a Glass: the four shade kernels' specular forms; the film
-// is splatted by launch_splat_mis over SpecDev::E or MisDev::E
-void launch_shade_spec(const ShadeSpecArgs &a, uint32_t max_items, hipStream_t st);
-void launch_shade_env_spec(const ShadeEnvSpecArgs &a, uint32_t max_items, hipStream_t st);
-void launch_shade_spec_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st);
-void launch_shade_env_spec_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st);
+// the unit kernels of akr_hip_environment_sample (sample) / akr_hip_environment_eval
 void launch_env_unit(bool sample, const EnvUnitArgs &a, hipStream_t st);
 void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, uint32_t *gate, hipStream_t st);
 void launch_store_word(const uint32_t *src, uint32_t *dst, hipStream_t st);
 void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st);
 void launch_ao_resolve(const AoResolveArgs &a, uint32_t max_items, hipStream_t st);
-// persistent path kernel forms: PATH_PLAIN / PATH_DEFER / PATH_SPEC (akr_path_forms.h)
-// leaf_one: PATH_PLAIN's product build with the one-triangle leaf phase (k_path) or without (k_path_general)
-// simple: the product builds' shading for tables of constant Diffuse / Emissive (shade_simple.h); the counting
-// builds and simple = false run the general shading
-void launch_path(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathArgs &a, uint32_t grid,
-                 hipStream_t st);
-int path_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple);  // of the product build launch_path would launch
-// with an environment light (option env_path): PATH_PLAIN's kernels over PathEnvArgs
-void launch_path_env(bool count, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid, hipStream_t st);
-int path_env_blocks_per_cu(bool tab, bool leaf_one, bool simple);
-// ... and every form's (option env_forms): PATH_DEFER / PATH_SPEC run k_path_defer_env /
-// k_path_spec_env, PATH_PLAIN is launch_path_env
-void launch_path_env_form(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid,
-                          hipStream_t st);
-int path_env_form_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple);
+// persistent path kernel forms: the kernel of the build key (path_build.h; the
+// table in DESIGN.md §0.5), with tab dropped when the tables do not fit LDS.  env is read by the key's
+// environment builds only (options env_path and env_forms)
+void launch_path(PathBuild b, const PathArgs &a, const AKR_GLOBAL EnvDev *env, uint32_t grid, hipStream_t st);
+int path_blocks_per_cu(PathBuild b);  // of the key's product build (count = false)
 bool path_tab_fits(int32_t n_mats, int32_t n_lights);
 void launch_check_weights(const float4 *film, uint32_t n, float expect, uint32_t *bad, hipStream_t st);
 void launch_merge_film(const float4 *film, const uint32_t *pixel, const uint32_t *order, uint32_t n, int32_t width,

@@ -4008,24 +4008,29 @@ int trace_blocks_per_cu(int mode) {
     return nb;
 }
 
-void launch_raygen(const RaygenArgs &a, hipStream_t st) {
-    if (a.n == 0) return;
-    hipLaunchKernelGGL(k_raygen, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
+// One thread per item in blocks of kBlock; nothing to launch for no items
+template <class K, class... A>
+static void launch_flat(K kernel, uint64_t n, hipStream_t st, const A &...args) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(kBlock), 0, st, args...);
 }
-void launch_shade(const ShadeArgs &a, uint32_t max_items, hipStream_t st) {
+
+void launch_raygen(const RaygenArgs &a, hipStream_t st) { launch_flat(k_raygen, a.n, st, a); }
+void launch_shade(ShadeBuild b, const ShadeArgs &s, const EnvDev *env, const MisDev *m, const SpecDev *d, uint32_t max_items,
+                  hipStream_t st) {
     if (max_items == 0) return;
     const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
-    hipLaunchKernelGGL(k_shade, grid, dim3(kShadeBlock), 0, st, a);
-}
-void launch_shade_env(const ShadeEnvArgs &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
-    hipLaunchKernelGGL(k_shade_env, grid, dim3(kShadeBlock), 0, st, a);
+    auto go = [&](auto kernel, const auto &a) { hipLaunchKernelGGL(kernel, grid, dim3(kShadeBlock), 0, st, a); };
+    // under MIS the via_delta bit rides in the carried record, so the specular MIS forms take the MIS arguments
+    if (b.mis && b.env) go(b.spec ? k_shade_env_spec_mis : k_shade_env_mis, ShadeEnvMisArgs{s, *env, *m});
+    else if (b.mis) go(b.spec ? k_shade_spec_mis : k_shade_mis, ShadeMisArgs{s, *m});
+    else if (b.spec && b.env) go(k_shade_env_spec, ShadeEnvSpecArgs{s, *env, *d});
+    else if (b.spec) go(k_shade_spec, ShadeSpecArgs{s, *d});
+    else if (b.env) go(k_shade_env, ShadeEnvArgs{s, *env});
+    else go(k_shade, s);
 }
 void launch_env_unit(bool sample, const EnvUnitArgs &a, hipStream_t st) {
-    if (a.n == 0) return;
-    if (sample) hipLaunchKernelGGL(k_env_sample, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL(k_env_eval, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
+    launch_flat(sample ? k_env_sample : k_env_eval, a.n, st, a);
 }
 void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, uint32_t *gate, hipStream_t st) {
     hipLaunchKernelGGL(k_pick_form, dim3(1), dim3(64), 0, st, sum, thresh, gate);
@@ -4033,222 +4038,138 @@ void launch_pick_form(const unsigned long long *sum, unsigned long long thresh, 
 void launch_store_word(const uint32_t *src, uint32_t *dst, hipStream_t st) {
     hipLaunchKernelGGL(k_store_word, dim3(1), dim3(64), 0, st, src, dst);
 }
-void launch_shade_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
-    hipLaunchKernelGGL(k_shade_mis, grid, dim3(kShadeBlock), 0, st, a);
-}
-void launch_shade_env_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
-    hipLaunchKernelGGL(k_shade_env_mis, grid, dim3(kShadeBlock), 0, st, a);
-}
-template <class K, class A>
-static void launch_shade_kernel(K kernel, const A &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    const dim3 grid((uint32_t)((max_items + kShadeBlock - 1) / kShadeBlock));
-    hipLaunchKernelGGL(kernel, grid, dim3(kShadeBlock), 0, st, a);
-}
-void launch_shade_spec(const ShadeSpecArgs &a, uint32_t max_items, hipStream_t st) {
-    launch_shade_kernel(k_shade_spec, a, max_items, st);
-}
-void launch_shade_env_spec(const ShadeEnvSpecArgs &a, uint32_t max_items, hipStream_t st) {
-    launch_shade_kernel(k_shade_env_spec, a, max_items, st);
-}
-void launch_shade_spec_mis(const ShadeMisArgs &a, uint32_t max_items, hipStream_t st) {
-    launch_shade_kernel(k_shade_spec_mis, a, max_items, st);
-}
-void launch_shade_env_spec_mis(const ShadeEnvMisArgs &a, uint32_t max_items, hipStream_t st) {
-    launch_shade_kernel(k_shade_env_spec_mis, a, max_items, st);
-}
-void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    hipLaunchKernelGGL(k_ao_shade, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
-}
-void launch_ao_resolve(const AoResolveArgs &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    hipLaunchKernelGGL(k_ao_resolve, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
-}
-void launch_splat(const SplatArgs &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    hipLaunchKernelGGL(k_splat, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
-}
-void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st) {
-    if (max_items == 0) return;
-    hipLaunchKernelGGL(k_splat_mis, dim3(blocks_for(max_items)), dim3(kBlock), 0, st, a);
-}
-// The persistent path kernel for (kind, count, tab).  The compiler emits the instantiations in the order
-// they are named here, which is the order the code object has always held them in.
-// The counting builds shade with the general build whatever `simple` says.  Of PATH_PLAIN's product builds
-// k_path<false, TAB> is simple shading with the one-triangle leaf phase (the name the committed traffic
-// profile is found by); every other pair of (leaf_one, simple) is a k_path_general, whose leaf phase finds
-// the same hits, so a forced k_path on a complex scene runs k_path_general<TAB, false>.
+void launch_ao_shade(const AoShadeArgs &a, uint32_t max_items, hipStream_t st) { launch_flat(k_ao_shade, max_items, st, a); }
+void launch_ao_resolve(const AoResolveArgs &a, uint32_t max_items, hipStream_t st) { launch_flat(k_ao_resolve, max_items, st, a); }
+void launch_splat(const SplatArgs &a, uint32_t max_items, hipStream_t st) { launch_flat(k_splat, max_items, st, a); }
+void launch_splat_mis(const SplatMisArgs &a, uint32_t max_items, hipStream_t st) { launch_flat(k_splat_mis, max_items, st, a); }
+
+// The persistent path kernel of a canonical key (path_build.h; the table in DESIGN.md §0.5), in two functions
+// for the two argument types.  The compiler emits the instantiations in the order they are named here, first
+// path_kernel's and then path_env_kernel's, which is the order the code object has always held them in: a new
+// build is named after every kernel here.
 using PathKernel = void (*)(PathArgs);
-static PathKernel path_kernel(int kind, bool count, bool tab, bool leaf_one, bool simple) {
-    if (count && tab) {
-        if (kind == PATH_DEFER) return k_path_defer<true, true, false>;
-        if (kind == PATH_SPEC) return k_path_spec<true, true, false>;
+static PathKernel path_kernel(PathBuild b) {
+    const bool tab = b.tab;
+    if (b.count && tab) {
+        if (b.kind == PATH_DEFER) return k_path_defer<true, true, false>;
+        if (b.kind == PATH_SPEC) return k_path_spec<true, true, false>;
         return k_path<true, true>;
     }
-    if (count) {
-        if (kind == PATH_DEFER) return k_path_defer<true, false, false>;
-        if (kind == PATH_SPEC) return k_path_spec<true, false, false>;
+    if (b.count) {
+        if (b.kind == PATH_DEFER) return k_path_defer<true, false, false>;
+        if (b.kind == PATH_SPEC) return k_path_spec<true, false, false>;
         return k_path<true, false>;
     }
-    if (kind == PATH_SPEC) {
-        if (simple) return tab ? k_path_spec<false, true, true> : k_path_spec<false, false, true>;
+    if (b.kind == PATH_SPEC) {
+        if (b.simple) return tab ? k_path_spec<false, true, true> : k_path_spec<false, false, true>;
         return tab ? k_path_spec<false, true, false> : k_path_spec<false, false, false>;
     }
-    if (kind == PATH_DEFER) {
-        if (simple) return tab ? k_path_defer<false, true, true> : k_path_defer<false, false, true>;
+    if (b.kind == PATH_DEFER) {
+        if (b.simple) return tab ? k_path_defer<false, true, true> : k_path_defer<false, false, true>;
         return tab ? k_path_defer<false, true, false> : k_path_defer<false, false, false>;
     }
-    if (!simple) return tab ? k_path_general<true, false> : k_path_general<false, false>;
-    if (!leaf_one) return tab ? k_path_general<true, true> : k_path_general<false, true>;
+    if (!b.simple) return tab ? k_path_general<true, false> : k_path_general<false, false>;
+    if (!b.leaf_one) return tab ? k_path_general<true, true> : k_path_general<false, true>;
     return tab ? k_path<false, true> : k_path<false, false>;
 }
-void launch_path(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathArgs &a, uint32_t grid,
-                 hipStream_t st) {
-    if (grid == 0) return;
-    if (tab && !path_tab_fits(a.sc.n_mats, a.sc.n_lights)) tab = false;  // the LDS copy must hold every record
-    hipLaunchKernelGGL(path_kernel(kind, count, tab, leaf_one, simple), dim3(grid), dim3(kTraceBlock), 0, st, a);
-}
-int path_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple) {
-    int nb = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(kind, false, tab, leaf_one, simple),
-                                                                      kTraceBlock, 0);
-    if (e != hipSuccess || nb <= 0) nb = 1;
-    return nb;
-}
-// The environment's kernels (option env_path): PATH_PLAIN's set, chosen as path_kernel() chooses, and named
-// after every kernel above so that those keep their places in the code object
 using PathEnvKernel = void (*)(PathEnvArgs);
-static PathEnvKernel path_env_kernel(bool count, bool tab, bool leaf_one, bool simple) {
-    if (count) return tab ? k_path_env<true, true> : k_path_env<true, false>;
-    if (!simple) return tab ? k_path_env_general<true, false> : k_path_env_general<false, false>;
-    if (!leaf_one) return tab ? k_path_env_general<true, true> : k_path_env_general<false, true>;
-    return tab ? k_path_env<false, true> : k_path_env<false, false>;
-}
-void launch_path_env(bool count, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid, hipStream_t st) {
-    if (grid == 0) return;
-    if (tab && !path_tab_fits(a.p.sc.n_mats, a.p.sc.n_lights)) tab = false;  // the LDS copy must hold every record
-    hipLaunchKernelGGL(path_env_kernel(count, tab, leaf_one, simple), dim3(grid), dim3(kTraceBlock), 0, st, a);
-}
-int path_env_blocks_per_cu(bool tab, bool leaf_one, bool simple) {
-    int nb = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_env_kernel(false, tab, leaf_one, simple),
-                                                                      kTraceBlock, 0);
-    if (e != hipSuccess || nb <= 0) nb = 1;
-    return nb;
-}
-// PATH_DEFER's and PATH_SPEC's environment kernels (option env_forms), chosen as path_kernel() chooses theirs
-static PathEnvKernel path_env_form_kernel(int kind, bool count, bool tab, bool simple) {
-    if (kind == PATH_DEFER) {
-        if (count) return tab ? k_path_defer_env<true, true, false> : k_path_defer_env<true, false, false>;
-        if (simple) return tab ? k_path_defer_env<false, true, true> : k_path_defer_env<false, false, true>;
+static PathEnvKernel path_env_kernel(PathBuild b) {
+    const bool tab = b.tab;
+    if (b.kind == PATH_PLAIN) {
+        if (b.count) return tab ? k_path_env<true, true> : k_path_env<true, false>;
+        if (!b.simple) return tab ? k_path_env_general<true, false> : k_path_env_general<false, false>;
+        if (!b.leaf_one) return tab ? k_path_env_general<true, true> : k_path_env_general<false, true>;
+        return tab ? k_path_env<false, true> : k_path_env<false, false>;
+    }
+    if (b.kind == PATH_DEFER) {
+        if (b.count) return tab ? k_path_defer_env<true, true, false> : k_path_defer_env<true, false, false>;
+        if (b.simple) return tab ? k_path_defer_env<false, true, true> : k_path_defer_env<false, false, true>;
         return tab ? k_path_defer_env<false, true, false> : k_path_defer_env<false, false, false>;
     }
-    if (count) return tab ? k_path_spec_env<true, true, false> : k_path_spec_env<true, false, false>;
-    if (simple) return tab ? k_path_spec_env<false, true, true> : k_path_spec_env<false, false, true>;
+    if (b.count) return tab ? k_path_spec_env<true, true, false> : k_path_spec_env<true, false, false>;
+    if (b.simple) return tab ? k_path_spec_env<false, true, true> : k_path_spec_env<false, false, true>;
     return tab ? k_path_spec_env<false, true, false> : k_path_spec_env<false, false, false>;
 }
-void launch_path_env_form(bool count, int kind, bool tab, bool leaf_one, bool simple, const PathEnvArgs &a, uint32_t grid,
-                          hipStream_t st) {
-    if (kind == PATH_PLAIN) return launch_path_env(count, tab, leaf_one, simple, a, grid, st);
+void launch_path(PathBuild b, const PathArgs &a, const AKR_GLOBAL EnvDev *env, uint32_t grid, hipStream_t st) {
     if (grid == 0) return;
-    if (tab && !path_tab_fits(a.p.sc.n_mats, a.p.sc.n_lights)) tab = false;  // the LDS copy must hold every record
-    hipLaunchKernelGGL(path_env_form_kernel(kind, count, tab, simple), dim3(grid), dim3(kTraceBlock), 0, st, a);
+    if (b.tab && !path_tab_fits(a.sc.n_mats, a.sc.n_lights)) b.tab = false;  // the LDS copy must hold every record
+    b = canonical(b);
+    if (b.env) hipLaunchKernelGGL(path_env_kernel(b), dim3(grid), dim3(kTraceBlock), 0, st, PathEnvArgs{a, env});
+    else hipLaunchKernelGGL(path_kernel(b), dim3(grid), dim3(kTraceBlock), 0, st, a);
 }
-int path_env_form_blocks_per_cu(int kind, bool tab, bool leaf_one, bool simple) {
-    if (kind == PATH_PLAIN) return path_env_blocks_per_cu(tab, leaf_one, simple);
+int path_blocks_per_cu(PathBuild b) {
+    b.count = false;
+    b = canonical(b);
+    const void *kernel = b.env ? (const void *)path_env_kernel(b) : (const void *)path_kernel(b);
     int nb = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_env_form_kernel(kind, false, tab, simple),
-                                                                      kTraceBlock, 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kTraceBlock, 0);
     if (e != hipSuccess || nb <= 0) nb = 1;
     return nb;
 }
 void launch_check_weights(const float4 *film, uint32_t n, float expect, uint32_t *bad, hipStream_t st) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_check_weights, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, n, expect, bad);
+    launch_flat(k_check_weights, n, st, film, n, expect, bad);
 }
 void launch_merge_film(const float4 *film, const uint32_t *pixel, const uint32_t *order, uint32_t n, int32_t width,
                        float *rad, float *w, hipStream_t st) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_merge_film, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, pixel, order, n, width, rad, w);
+    launch_flat(k_merge_film, n, st, film, pixel, order, n, width, rad, w);
 }
 void launch_pilot_rays(const CameraDev &cam, const uint32_t *pixel, uint32_t n, uint32_t sub, float4 *rays,
                        hipStream_t st) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_pilot_rays, dim3(blocks_for(n)), dim3(kBlock), 0, st, cam, pixel, n, sub, rays);
+    launch_flat(k_pilot_rays, n, st, cam, pixel, n, sub, rays);
 }
 void launch_order_keys(const uint32_t *steps, uint32_t n, uint32_t shift, uint32_t cmax, uint32_t sub, uint32_t *key,
                        uint32_t *idx, hipStream_t st, unsigned long long *sum) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_order_keys, dim3(blocks_for(n)), dim3(kBlock), 0, st, steps, n, shift,
-                       cmax < kOrderClassMask ? cmax : kOrderClassMask, sub, key, idx, sum);
+    launch_flat(k_order_keys, n, st, steps, n, shift, cmax < kOrderClassMask ? cmax : kOrderClassMask, sub, key, idx, sum);
 }
 void launch_probe_cost(const uint4 *probe, uint32_t n, uint32_t *cost, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_probe_cost, dim3(blocks_for(n)), dim3(kBlock), 0, st, probe, n, cost);
+    launch_flat(k_probe_cost, n, st, probe, n, cost);
 }
 void launch_probe_seed(const uint32_t *seed, uint32_t n, uint4 *probe, hipStream_t st) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_probe_seed, dim3(blocks_for(n)), dim3(kBlock), 0, st, seed, n, probe);
+    launch_flat(k_probe_seed, n, st, seed, n, probe);
 }
 void launch_expand_pixels(const uint4 *tiles, uint32_t n_tiles, uint32_t n, uint32_t *pixel, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_expand_pixels, dim3(blocks_for(n)), dim3(kBlock), 0, st, tiles, n_tiles, n, pixel);
+    launch_flat(k_expand_pixels, n, st, tiles, n_tiles, n, pixel);
 }
 void launch_mask_count(const uint8_t *mask, uint32_t n, uint32_t *wcount, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_mask_count, dim3(blocks_for(n)), dim3(kBlock), 0, st, mask, n, wcount);
+    launch_flat(k_mask_count, n, st, mask, n, wcount);
 }
 void launch_mask_compact(const uint8_t *mask, uint32_t n, const uint32_t *woff, uint32_t *list, uint32_t *total,
                          hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_mask_compact, dim3(blocks_for(n)), dim3(kBlock), 0, st, mask, n, woff, list, total);
+    launch_flat(k_mask_compact, n, st, mask, n, woff, list, total);
 }
-void launch_fill_u32(uint32_t *p, uint32_t n, uint32_t v, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_fill_u32, dim3(blocks_for(n)), dim3(kBlock), 0, st, p, n, v);
-}
+void launch_fill_u32(uint32_t *p, uint32_t n, uint32_t v, hipStream_t st) { launch_flat(k_fill_u32, n, st, p, n, v); }
 void launch_count_add(uint32_t *count, const uint32_t *list, uint32_t n, uint32_t spp, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_count_add, dim3(blocks_for(n)), dim3(kBlock), 0, st, count, list, n, spp);
+    launch_flat(k_count_add, n, st, count, list, n, spp);
 }
 void launch_check_counts(const float4 *film, const uint32_t *count, uint32_t n, uint32_t *bad, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_check_counts, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, count, n, bad);
+    launch_flat(k_check_counts, n, st, film, count, n, bad);
 }
 void launch_count_range(const uint32_t *count, const uint32_t *list, uint32_t n, uint32_t *out, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_count_range, dim3(blocks_for(n)), dim3(kBlock), 0, st, count, list, n, out);
+    launch_flat(k_count_range, n, st, count, list, n, out);
 }
 void launch_init_seed(const uint32_t *pixel, uint32_t n, int32_t width, uint32_t *seed, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_init_seed, dim3(blocks_for(n)), dim3(kBlock), 0, st, pixel, n, width, seed);
+    launch_flat(k_init_seed, n, st, pixel, n, width, seed);
 }
 void launch_probe_fill(const uint32_t *seed, uint32_t n, uint4 *probe, uint32_t flags, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_probe_fill, dim3(blocks_for(n)), dim3(kBlock), 0, st, seed, n, probe, flags);
+    launch_flat(k_probe_fill, n, st, seed, n, probe, flags);
 }
 void launch_adaptive_test(const float4 *film, float4 *prev, uint32_t n, float threshold, float *strip_err,
                           uint8_t *strip_active, uint8_t *mask, hipStream_t st) {
-    if (n)
-        hipLaunchKernelGGL(k_adaptive_test, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, prev, n, threshold, strip_err,
-                           strip_active, mask);
+    launch_flat(k_adaptive_test, n, st, film, prev, n, threshold, strip_err, strip_active, mask);
 }
 void launch_unpack(const float4 *film, uint32_t n, float *rad, float *w, hipStream_t st) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_unpack_film, dim3(blocks_for(n)), dim3(kBlock), 0, st, film, n, rad, w);
+    launch_flat(k_unpack_film, n, st, film, n, rad, w);
 }
 void launch_feature_rays(const CameraDev &cam, const uint32_t *pixel, uint32_t n, uint32_t *seed, bool first,
                          float4 *rays, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_feature_rays, dim3(blocks_for(n)), dim3(kBlock), 0, st, cam, pixel, n, seed, first ? 1 : 0, rays);
+    launch_flat(k_feature_rays, n, st, cam, pixel, n, seed, first ? 1 : 0, rays);
 }
-void launch_feature_shade(const FeatureArgs &a, hipStream_t st) {
-    if (a.n) hipLaunchKernelGGL(k_feature_shade, dim3(blocks_for(a.n)), dim3(kBlock), 0, st, a);
-}
+void launch_feature_shade(const FeatureArgs &a, hipStream_t st) { launch_flat(k_feature_shade, a.n, st, a); }
 // the thin lens: the caller launches these only for a lens with radius > 0 and focal > 0
-void launch_raygen_lens(const RaygenLensArgs &a, hipStream_t st) {
-    if (a.r.n == 0) return;
-    hipLaunchKernelGGL(k_raygen_lens, dim3(blocks_for(a.r.n)), dim3(kBlock), 0, st, a);
-}
+void launch_raygen_lens(const RaygenLensArgs &a, hipStream_t st) { launch_flat(k_raygen_lens, a.r.n, st, a); }
 void launch_feature_rays_lens(const CameraDev &cam, const LensDev &lens, const uint32_t *pixel, uint32_t n, uint32_t *seed,
                               bool first, float4 *rays, hipStream_t st) {
-    if (n)
-        hipLaunchKernelGGL(k_feature_rays_lens, dim3(blocks_for(n)), dim3(kBlock), 0, st, cam, lens, pixel, n, seed,
-                           first ? 1 : 0, rays);
+    launch_flat(k_feature_rays_lens, n, st, cam, lens, pixel, n, seed, first ? 1 : 0, rays);
 }
 
 }  // namespace akr

@@ -119,6 +119,16 @@ def test_builders_and_leaf_sizes_equal_golden(hip_ctx_factory, name, builder, ma
         render_and_compare(ctx, name, f"{builder} max_leaf {max_leaf}")
 
 
+def test_one_triangle_leaves_with_the_tables_in_memory(hip_ctx_factory):
+    """cornell, max_leaf_size 1, path_tab 0: k_path_env<false, false>.  The tests above render that tree with the
+    tables in LDS only, and the tables in memory on the default tree (k_path_env_general) only."""
+    with hip_ctx_factory(0) as ctx:
+        upload(ctx, "cornell", max_leaf_size=1, n_threads=16)
+        assert np.all(leaf_counts(ctx.accel_export()[0]) == 1)
+        set_options(ctx, {**ON, "path_tab": 0})
+        render_and_compare(ctx, "cornell", "max_leaf 1, path_tab 0", configs=ME.CONFIGS["cornell"][2:3])
+
+
 # ---- 3. the auto rule
 @pytest.mark.parametrize("name", SCENES)
 def test_auto_rule(hip_ctx_factory, name):
